@@ -8,7 +8,16 @@ over the whole bucket.  value = whole-job GB/s = world_size x (N+1) x count x
 source/compute.h:197-203).  Multi-GPU: every rank reduces its own bucket
 (replicas, weak scaling -- the stage is per-GPU local).
 
-Extra objects on the JSON line:
+A plain run (`--gpus G --steps K --warmup W`) sets up the bucket, warms up,
+times the K steps and prints the line: metric, value, unit, ms_per_step (the
+slowest rank's wall time per timed step) and the kernel times its own events
+gave.  `--dump-outputs DIR` also writes the last timed step's output as
+DIR/out.npy (float32; above 2^23 elements a fixed seeded sample,
+dump_indices).  Everything else -- parity checks, measured ceilings, the
+misaligned and layout A/Bs, the CPU baseline, the config-5 leg at N > 1 --
+runs only with `--full`.
+
+Extra objects on the JSON line with --full:
   roofline      achieved = algorithmic bytes per launch / mean kernel time from
                 HIP events on the launch stream; peak = 8000 GB/s (MI355X HBM3E
                 spec); traffic = PMC HBM bytes per launch from the committed
@@ -624,6 +633,34 @@ def traffic_from_profiles(n, count, kernel=DEFAULT_KERNEL, run_kernel_ms=None):
     return best
 
 
+DUMP_MAX_ELEMS = 1 << 23  # 32 MiB of float32 per array, inside the 64 MB a dump may take
+
+
+def dump_indices(count, limit=DUMP_MAX_ELEMS, seed=SEED):
+    """Which elements of a `count`-element output a dump holds: all of them up
+    to `limit`, else `limit` sorted indices drawn once from a seeded
+    generator (the first and the last element always among them) -- a
+    function of (count, limit, seed) only, so two builds dump the same
+    elements.  None means all."""
+    if count <= limit:
+        return None
+    idx = np.random.default_rng(seed).integers(0, count, limit, dtype=np.int64)
+    idx[:2] = [0, count - 1]
+    idx.sort()
+    return idx
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: each device tensor a caller of the timed path receives,
+    as directory/<name>.npy in float32 (the elements of dump_indices)."""
+    os.makedirs(directory, exist_ok=True)
+    for name, t in arrays.items():
+        idx = dump_indices(t.numel())
+        if idx is not None:
+            t = t[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(directory, name + ".npy"), t.float().cpu().numpy())
+
+
 # ------------------------------------------------------------------ main ----
 
 # flag -> (tools/bench_modes.py function, help)
@@ -640,7 +677,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--n", type=int, default=8, help="inputs per bucket")
     ap.add_argument("--log2count", type=int, default=28, help="elements per input = 2^x")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the parity checks, the measured HBM ceilings, the misaligned "
+                         "and layout A/Bs, the CPU baseline and (N > 1) the config-5 leg, and print the full line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (float32; a fixed seeded sample "
+                         "of an output above 32 MiB)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline leg")
     ap.add_argument("--cpu-budget", type=float, default=10.0)
     ap.add_argument("--cpu-placement", default="", help="CPU baseline thread placement: " + " | ".join(CPU_POLICIES)
                     + " (default HICCL_CPU_PLACEMENT or l3spread); --cpu-only: a comma list")
@@ -690,7 +733,7 @@ def main():
         return 0
 
     c5 = None
-    if os.environ.get("WORLD_SIZE", "1") != "1" and not args.no_c5:
+    if args.full and os.environ.get("WORLD_SIZE", "1") != "1" and not args.no_c5:
         # before this process touches a GPU: the MPI job owns every GPU meanwhile
         c5 = c5_leg(args)
     dist = Dist(args.gpus)
@@ -714,17 +757,22 @@ def main():
     value = whole_job_gbps(dist.world, bytes_step, args.steps, wall_max)
     kern_s = float(np.mean(kms)) * 1e-3
     achieved = bytes_step / kern_s / 1e9
+    if args.dump_outputs and dist.rank == 0:
+        dump_outputs(args.dump_outputs, {"out": out})
+    # A plain run ends with its line here; everything from here to the line
+    # that is not the headline's own arithmetic runs under --full only.
+    full = args.full
 
     # full-bucket parity (N = 1, rank 0): the GPU's whole output against the
     # reference's own CPU reduce_kernel on the same generator and seed, done
     # by the CPU baseline leg below
     gpu_out = None
-    if dist.rank == 0 and dist.world == 1 and not args.no_cpu and cfg is None:
+    if full and dist.rank == 0 and dist.world == 1 and not args.no_cpu and cfg is None:
         gpu_out = out.cpu().numpy()
     # parity spot check of this very output against the oracle generator
     parity = None
     ora_so = os.path.join(ROOT, "oracle", "liboracle.so")
-    if os.path.exists(ora_so):
+    if full and os.path.exists(ora_so):
         ora = ctypes.CDLL(ora_so)
         idx = np.random.default_rng(dist.rank).integers(0, count, 1024).astype(np.uint64)
         exp = np.empty(len(idx), np.float32)
@@ -735,21 +783,21 @@ def main():
         parity = bool(np.array_equal(got.view(np.uint32), exp.view(np.uint32)))
         if not parity:
             log("bench: PARITY FAILURE against the oracle sample")
-    mix_gbps = mix_ceiling(ins, out, count) if dist.rank == 0 else None
-    read_gbps = mix_ceiling(ins, out, count, mode=1) if dist.rank == 0 else None
-    write_gbps = mix_ceiling(ins, out, count, mode=2) if dist.rank == 0 else None
+    mix_gbps = mix_ceiling(ins, out, count) if full and dist.rank == 0 else None
+    read_gbps = mix_ceiling(ins, out, count, mode=1) if full and dist.rank == 0 else None
+    write_gbps = mix_ceiling(ins, out, count, mode=2) if full and dist.rank == 0 else None
     del ins, out
     torch.cuda.empty_cache()
 
     parity = bool(dist.max(0.0 if parity in (True, None) else 1.0) == 0.0) if parity is not None else None
-    copy_gbps = copy_ceiling() if dist.rank == 0 else None
+    copy_gbps = copy_ceiling() if full and dist.rank == 0 else None
     misaligned = (c2_misaligned(n, count, args.steps, args.warmup, headline_s=kern_s)
-                  if dist.rank == 0 and cfg is None and not args.no_misaligned else None)
+                  if full and dist.rank == 0 and cfg is None and not args.no_misaligned else None)
     layout_ab = (c2_layout_ab(n, count, args.steps, args.warmup, headline_s=kern_s)
-                 if dist.rank == 0 and cfg is None and not args.no_misaligned else None)
-    prof = traffic_from_profiles(n, count, run_kernel_ms=kern_s * 1e3) if cfg is None else None
+                 if full and dist.rank == 0 and cfg is None and not args.no_misaligned else None)
+    prof = traffic_from_profiles(n, count, run_kernel_ms=kern_s * 1e3) if full and cfg is None else None
     cpu, parity_full = None, None
-    if dist.rank == 0 and dist.world == 1 and not args.no_cpu:
+    if full and dist.rank == 0 and dist.world == 1 and not args.no_cpu:
         cpu, parity_full = cpu_baseline(n, count, args.cpu_budget, gpu_out, policy=args.cpu_placement or None,
                                         threads=args.cpu_threads or None)
         if parity_full and not parity_full["ok"]:
@@ -778,6 +826,7 @@ def main():
         "scaling": "weak",
         "vs_baseline": None,
         "dtype": "f32",
+        "full": full,  # False: the plain run; the measured ceilings, baselines and checks below are null
         "data": "synthetic (uniform [-1,1) counter-hash, device-generated)",
         "config": {"workload": f"C2: {n} inputs x 2^{args.log2count} fp32 ({count * 4 >> 20} MiB/input) -> 1 output, "
                                "device-resident, one hiccl_reduce launch per step",

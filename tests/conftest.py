@@ -104,11 +104,15 @@ def oracle():
 
 
 def load_golden(name):
-    z = np.load(os.path.join(GOLDEN, f"{name}.npz"), allow_pickle=False)
+    """Every case of fixture `name`: <name>.npz and its <name>.partN.npz
+    files (make_golden.save splits a large set over several files)."""
+    parts = sorted(f for f in os.listdir(GOLDEN) if f.startswith(f"{name}.part") and f.endswith(".npz"))
     cases = {}
-    for key in z.files:
-        case, part = key.rsplit("/", 1)
-        cases.setdefault(case, {})[part] = z[key]
+    for fname in [f"{name}.npz"] + parts:
+        z = np.load(os.path.join(GOLDEN, fname), allow_pickle=False)
+        for key in z.files:
+            case, part = key.rsplit("/", 1)
+            cases.setdefault(case, {})[part] = z[key]
     return cases
 
 

@@ -222,14 +222,26 @@ def main():
     print("wrote", sorted(manifest["files"]))
 
 
+PART_BYTES = 768 << 10  # arrays per fixture file: every committed file stays under 1 MiB
+
+
 def save(name, cases, manifest, pinned_by):
-    arrs = {}
+    """<name>.npz, and <name>.part2.npz ... when the cases hold more than
+    PART_BYTES: cases in order, a new file when the next case would not fit
+    (conftest.load_golden reads the parts back as one set)."""
+    parts, size = [{}], 0
     for k, (x, y) in cases.items():
-        arrs[f"{k}/in"] = x
-        arrs[f"{k}/out"] = y
-    path = os.path.join(HERE, f"{name}.npz")
-    np.savez_compressed(path, **arrs)
-    manifest["files"][f"{name}.npz"] = {"sha256": sha(path), "cases": len(cases), "pinned_by": pinned_by}
+        if parts[-1] and size + x.nbytes + y.nbytes > PART_BYTES:
+            parts.append({})
+            size = 0
+        parts[-1][f"{k}/in"] = x
+        parts[-1][f"{k}/out"] = y
+        size += x.nbytes + y.nbytes
+    for i, arrs in enumerate(parts):
+        fname = f"{name}.npz" if i == 0 else f"{name}.part{i + 1}.npz"
+        path = os.path.join(HERE, fname)
+        np.savez_compressed(path, **arrs)
+        manifest["files"][fname] = {"sha256": sha(path), "cases": len(arrs) // 2, "pinned_by": pinned_by}
 
 
 if __name__ == "__main__":

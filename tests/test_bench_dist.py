@@ -494,6 +494,24 @@ def test_driver_line_keeps_every_c5_mode_at_n8(failing):
         assert k in ab
 
 
+def test_dump_indices_fixed_sample():
+    """--dump-outputs: an output up to the limit is dumped whole; above it the
+    same sorted sample every time (a function of the size and the seed), the
+    first and last element in it, every index in range, and the float32 dump
+    of it inside 64 MB."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    assert bench.dump_indices(0) is None and bench.dump_indices(bench.DUMP_MAX_ELEMS) is None
+    count = 1 << 28
+    a, b = bench.dump_indices(count), bench.dump_indices(count)
+    assert np.array_equal(a, b) and a.dtype == np.int64 and len(a) == bench.DUMP_MAX_ELEMS
+    assert a[0] == 0 and a[-1] == count - 1 and np.all(np.diff(a) >= 0)
+    assert len(a) * 4 <= 64e6
+    small = bench.dump_indices(bench.DUMP_MAX_ELEMS + 1)
+    assert small.min() == 0 and small.max() == bench.DUMP_MAX_ELEMS
+
+
 def test_traffic_profile_cited_fits_the_run(tmp_path, monkeypatch):
     """bench.traffic_from_profiles cites the newest PMC profile of the
     headline kernel whose rocprofv3 kernel time is at or below this run's

@@ -13,22 +13,23 @@ export TMPDIR=/tmp
 tag=$1
 shift
 steps=${*:-gputest bench c3vsc2 roundtrip}
-mkdir -p gpurun_out
+out=${HICCL_MEASURE_OUT:-measure_out}  # where the logs and result lines go
+mkdir -p "$out"
 for s in $steps; do
   case $s in
     gputest)
       timeout -k 10 900 python3 -u -m pytest tests -m gpu -x -v --timeout 240 --timeout-method thread \
-        --durations 30 > "gpurun_out/${tag}_gputest.log" 2>&1 ;;
+        --durations 30 > "$out/${tag}_gputest.log" 2>&1 ;;
     bench)
-      timeout -k 10 300 python3 bench.py > "gpurun_out/${tag}_bench.jsonl" 2> "gpurun_out/${tag}_bench.err" ;;
+      timeout -k 10 300 python3 bench.py --full > "$out/${tag}_bench.jsonl" 2> "$out/${tag}_bench.err" ;;
     c3vsc2)
       timeout -k 10 400 python3 bench.py --c3vsc2 --rounds 5 --steps 10 --warmup 3 \
-        > "gpurun_out/${tag}_c3_vs_c2.jsonl" 2> "gpurun_out/${tag}_c3_vs_c2.err" ;;
+        > "$out/${tag}_c3_vs_c2.jsonl" 2> "$out/${tag}_c3_vs_c2.err" ;;
     progstep)
-      timeout -k 10 300 python3 bench.py --progstep > "gpurun_out/${tag}_progstep.jsonl" 2> "gpurun_out/${tag}_progstep.err" ;;
+      timeout -k 10 300 python3 bench.py --progstep > "$out/${tag}_progstep.jsonl" 2> "$out/${tag}_progstep.err" ;;
     roundtrip)
-      timeout -k 10 400 python3 bench.py --roundtrip > "gpurun_out/${tag}_roundtrip.jsonl" \
-        2> "gpurun_out/${tag}_roundtrip.err" ;;
+      timeout -k 10 400 python3 bench.py --roundtrip > "$out/${tag}_roundtrip.jsonl" \
+        2> "$out/${tag}_roundtrip.err" ;;
     *) echo "unknown step $s"; exit 2 ;;
   esac
   echo "measure: $s done"
