@@ -14,20 +14,41 @@ all: $(LIB) $(PROBE) cpp oracle
 $(PROBE): tools/hbm_probe.hip
 	$(HIPCC) $(HIPFLAGS) -o $@ $<
 
+# The library: one kernel translation unit (reduce.hip, minutes to compile)
+# and the host files (seconds each), as objects under build/obj, linked once.
+# Both are compiled by hipcc's clang at -O3 without fast-math (the AUTO rules
+# compare doubles) and without per-thread default streams; the host files as
+# plain C++, so they carry no device code.
+CSRC = hiccl_amd/csrc
+OBJDIR = build/obj
+OBJFLAGS = -O3 -fPIC -std=c++17 -Wall -MMD -MP
+LIB_HOST = runtime policy oneshot plan host_pipe signal program util
+LIB_OBJS = $(OBJDIR)/reduce.o $(LIB_HOST:%=$(OBJDIR)/%.o)
+
 # The atomic optimizer rewrites the one-lane unit-ticket grab into a
 # wave-reduction whose result is read back at once (s_waitcnt vmcnt(0) at the
 # top of every unit); without it the wait lands after the unit's last add.
 LIBFLAGS = -mllvm -amdgpu-atomic-optimizer-strategy=None
 
-$(LIB): hiccl_amd/csrc/reduce.hip include/hiccl_reduce.h
-	$(HIPCC) $(HIPFLAGS) $(LIBFLAGS) -o $@ $<
+$(OBJDIR)/reduce.o: $(CSRC)/reduce.hip
+	@mkdir -p $(OBJDIR)
+	$(HIPCC) --offload-arch=$(ARCH) $(OBJFLAGS) $(LIBFLAGS) -c -o $@ $<
+
+$(OBJDIR)/%.o: $(CSRC)/%.cpp
+	@mkdir -p $(OBJDIR)
+	$(HIPCC) -x c++ -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include $(OBJFLAGS) -c -o $@ $<
+
+$(LIB): $(LIB_OBJS) $(CSRC)/exports.map
+	$(HIPCC) --offload-arch=$(ARCH) -fPIC -shared -Wl,--version-script=$(CSRC)/exports.map -o $@ $(LIB_OBJS)
+
+-include $(LIB_OBJS:.o=.d)
 
 # oracle/_ref/collectives_main_hip links the HIP library: build it first
 oracle: $(LIB)
 	$(MAKE) -C oracle
 
 clean:
-	rm -f $(LIB)
+	rm -f $(LIB) $(LIB_OBJS) $(LIB_OBJS:.o=.d)
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle clean

@@ -1,0 +1,157 @@
+// hiccl_amd/csrc/kernels.h -- all the host files see of the gfx950 kernels
+// (reduce.hip): the kernels' argument structs, the constants both sides need,
+// the kernel-table lookups and the launch wrappers of the plain kernels.
+#pragma once
+
+#include <hip/hip_runtime_api.h>
+
+#include <stddef.h>
+#include <stdint.h>
+
+// Library-internal: nothing in here is exported from libhiccl_reduce.so.
+namespace hiccl_impl __attribute__((visibility("hidden"))) {
+
+constexpr int kPacket = 16;  // bytes per lane per load
+
+// Cache policy, POL = 10*store + load.  load: 0 default, 1 nt (aux bit 1),
+// 2 system scope (sc0 sc1: coherent with a peer GPU's writes -- the
+// reading XCD's L2 does not serve a line of peer memory it cached earlier).
+// store: 0 default, 1 nt, 2 sc1 (aux bit 4: write-through, line dropped
+// from the XCD L2), 3 system scope (sc0 sc1: written through to the memory
+// that owns the line, a peer GPU's HBM over xGMI included -- nt stores are
+// not write-through and may sit dirty in this XCD's L2 after the kernel).
+// The system-scope forms are the PEER policies of plans whose outputs or
+// inputs live in another GPU's memory (hiccl_reduce_plan_set_peer).
+constexpr int kPolLoadSys = 2;
+constexpr int kPolStoreSys = 3;
+constexpr int kDefPol = 11;  // nt loads, nt stores
+
+// Engine shapes, chosen from on-device sweeps:
+//  tile   256 lanes x 4 packets (16 KiB per input per tile), for computes too
+//         small to give every CU several phased chunks;
+//  phase  512 lanes x P packets (P = phase_p: 16, or 8 where the accumulator
+//         of a packet takes 8 VGPRs -- bf16 WIDE -- or the adds get
+//         reassociated: int32) -- 128 KiB per input per chunk (64 KiB at P = 8).
+// Both: nt loads and nt stores, one workgroup per CU, grid-stride.  Plan
+// kernels run the TILE engine at kDefBlock lanes only.
+constexpr int kDefBlock = 256;
+constexpr int kDefUnroll = 4;
+constexpr int kPhBlock = 512;
+
+constexpr int kMaxArgInputs = 64;  // kernarg pointer table (512 B)
+
+struct SingleArgs {
+  char *out;          // raw output pointer
+  uint64_t npkt;      // body packets
+  uint64_t ntiles;    // >= 1
+  uint32_t n;         // inputs
+  uint32_t head;      // scalar elements before the body
+  uint32_t tail;      // scalar elements after the body
+  uint32_t order;     // log2 of the tile-order segments (0: linear; tile_order)
+  uint32_t *sched;    // dynamic unit counter {ticket, done}, or NULL: static grid-stride
+  uint32_t grab;      // units per ticket (dynamic schedule), >= 1
+  uint32_t drain;     // 1: wait for a unit's stores before the next unit's loads
+  const char *in[kMaxArgInputs];
+};
+
+// Descriptor of one compute in a batched plan (device memory).
+struct PlanDesc {
+  char *out;
+  uint64_t npkt;
+  uint64_t tile_begin;  // first global unit of this compute
+  uint32_t n, head, tail, pad;
+};
+static_assert(sizeof(PlanDesc) == 40, "PlanDesc layout");
+
+// A plan launch.  One device block holds [desc | ptrs | unit_comp]:
+//   desc[c]                  compute c
+//   ptrs[c * stride + k]     input k of compute c (stride = the plan's max n)
+//   unit_comp[t]             the compute owning global unit t (NULL: compute 0)
+// so a workgroup reaches a unit's input pointers in two dependent scalar
+// loads: unit_comp[t], then desc[c] and ptrs[c * stride ...] side by side.
+struct PlanArgs {
+  const PlanDesc *desc;
+  const char *const *ptrs;
+  const uint32_t *unit_comp;
+  uint64_t t_begin, t_end;
+  uint32_t *sched;  // dynamic unit counter, or NULL
+  uint32_t stride, grab;
+};
+
+constexpr int kMaxFlags = 64;  // signal and wait flags per launch (one per lane)
+
+// Several signal/wait phases in ONE launch, executed in order: phase p
+// stores its epoch to its flags (system-scope release), then waits for its
+// flags (relaxed polls, then a system-scope acquire fence); phase
+// p + 1 starts after every wait of phase p has finished.  The transport queues the consecutive signal/wait steps of
+// a stream-ordered pipeline (a step's done tokens, the next step's readies)
+// into one such launch instead of one launch each: same order of every
+// operation on the stream, fewer kernel boundaries (~1.5-1.9 us each).
+constexpr int kMaxPhases = 8;
+
+struct SigPhaseArgs {
+  uint32_t *sig[kMaxFlags];
+  const uint32_t *wait[kMaxFlags];
+  uint32_t *err;
+  const uint32_t *epoch_dev;  // NULL, or a device word added to every epoch at run time (graph replays)
+  uint64_t timeout_ticks;
+  uint32_t nphase;
+  uint32_t light;  // 1: relaxed stores and polls, no fences (HICCL_PROG_FENCES, as the programs' prologue)
+  uint32_t sig_end[kMaxPhases];   // phase p signals sig[sig_end[p-1] .. sig_end[p])
+  uint32_t wait_end[kMaxPhases];  // and waits for wait[wait_end[p-1] .. wait_end[p])
+  uint32_t epoch[kMaxPhases];
+};
+
+constexpr int kProgMaxPhases = 64;
+constexpr int kProgBlock = 256;
+
+struct ProgPhase {
+  uint32_t sig_begin, sig_end, wait_begin, wait_end;
+};
+
+struct ProgArgs {
+  const PlanDesc *desc;  // computes of the unit batch; pad bit 0: exact byte copy, bits 1-2: peer flags
+  const char *const *ptrs;
+  const uint32_t *unit_comp;
+  const ProgPhase *phase;
+  uint32_t *const *sig;
+  const uint32_t *const *wait;
+  uint64_t *gate;  // workgroup 0 stores the launch's sequence number here after the phases
+  uint32_t *err;
+  const uint32_t *epoch_dev;
+  uint64_t timeout_ticks;
+  uint64_t nunits;
+  uint32_t stride, nphase;
+  uint64_t seq;  // this launch's gate value (+ *epoch_dev); never reused, see hiccl_program_launch
+  uint32_t light;  // 1: relaxed token stores, no fences in the prologue (HICCL_PROG_FENCES, prog_light())
+  uint32_t epoch[kProgMaxPhases];  // per launch: phase p stores / awaits epoch[p] (+ *epoch_dev)
+};
+
+// ---- what reduce.hip's one list of element types answers (dtype: HICCL_*,
+// acc: HICCL_ACC_*)
+
+size_t esize(int dtype);            // bytes per element, 0 for an unknown dtype
+bool tuned_type(int dtype, int acc);  // a headline type (f32, bf16 native): the full tuning table
+int phase_p(int dtype, int acc);    // packets per lane of the PHASE engine's default chunk
+
+// ---- kernel tables: the launcher of a shape, or NULL where no kernel has it
+// (engine: HICCL_ENGINE_TILE / _PHASE; pol: 10*store + load)
+
+typedef void (*single_fn)(SingleArgs, dim3, hipStream_t);
+typedef void (*plan_fn)(const PlanArgs &, dim3, hipStream_t);
+typedef void (*prog_fn)(const ProgArgs &, dim3, hipStream_t);
+
+single_fn pick_single(int dtype, int acc, int engine, int block, int unroll, int pol);
+plan_fn pick_plan(int dtype, int acc, int engine, int unroll, int pol = kDefPol);
+prog_fn pick_prog(int dtype, int unroll);
+
+// ---- the plain kernels
+
+void launch_sigwait_phases(const SigPhaseArgs &a, hipStream_t s);
+void launch_counter_add(uint32_t *ctr, uint32_t v, hipStream_t s);
+// false: no fill kernel for this dtype (FLOAT32 / FLOAT64 / BFLOAT16 only)
+bool launch_fill(int dtype, unsigned blocks, hipStream_t s, char *out, uint64_t count, uint64_t key, uint64_t first);
+void launch_copy(unsigned blocks, hipStream_t s, void *dst, const void *src, uint64_t npkt);
+void launch_copy_bytes(hipStream_t s, char *dst, const char *src, uint64_t nbytes);
+
+}  // namespace hiccl_impl

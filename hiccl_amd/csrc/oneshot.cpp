@@ -1,0 +1,150 @@
+// hiccl_amd/csrc/oneshot.cpp -- hiccl_reduce*: one reduction per call, and
+// hiccl_reduce_auto_choice*: what AUTO would pick for it.
+#include <string.h>
+
+#include "plan.h"
+
+using namespace hiccl_impl;
+
+namespace {
+
+uint32_t log2u(int v) {
+  uint32_t l = 0;
+  while (v > 1) {
+    v >>= 1;
+    l++;
+  }
+  return l;
+}
+
+// Large-n one-shot path: stage the pointer table in stream-ordered device
+// memory and run it as a one-compute plan.
+int reduce_via_table(int dtype, const Cfg &c, void *out, const void *const *in, int n, size_t count,
+                     hipStream_t s) {
+  DescTable t((size_t)n, unit_pkts(c.engine, dtype, c.acc, c.unroll));
+  t.add(out, in, (size_t)n, count, esize(dtype));
+  const std::vector<char> host = t.image();
+  char *dmem = nullptr;
+  if (int e = check_hip(hipMallocAsync((void **)&dmem, host.size(), s), "hiccl_reduce: hipMallocAsync")) return e;
+  // hipMemcpyAsync from pageable memory returns once the source is consumed,
+  // so `host` may go out of scope (never under capture: refused by the caller)
+  if (int e = check_hip(hipMemcpyAsync(dmem, host.data(), host.size(), hipMemcpyHostToDevice, s),
+                        "hiccl_reduce: table upload")) {
+    (void)hipFreeAsync(dmem, s);
+    return e;
+  }
+  PlanArgs a;
+  memset(&a, 0, sizeof(a));
+  t.bind(a, dmem);
+  a.t_begin = 0;
+  a.t_end = t.units;
+  // the store form oneshot_cfg decided: write-through by size or on request
+  // (store_policy 4), else nt
+  const int pol = plan_pol(c.store == kPolStoreSys ? HICCL_PEER_STORES : 0);
+  if (int e = launch_plan(a, dtype, c, n, current_device(), s, pol)) {
+    (void)hipFreeAsync(dmem, s);  // nothing launched reads it
+    return e;
+  }
+  return check_hip(hipFreeAsync(dmem, s), "hiccl_reduce: hipFreeAsync");
+}
+
+}  // namespace
+
+extern "C" {
+
+int hiccl_reduce_ex(int dtype, void *out, const void *const *in, int n, size_t count,
+                    void *stream, const hiccl_reduce_config_t *cfg) {
+  const size_t esz = esize(dtype);
+  if (!esz) return fail(hipErrorInvalidValue, "hiccl_reduce: unknown dtype " + std::to_string(dtype));
+  if (count == 0) return 0;
+  if (dtype == HICCL_BYTES && n != 1) return fail(hipErrorInvalidValue, "hiccl_reduce: HICCL_BYTES copies need n == 1");
+  if (int e = check_buffers(out, in, n, count, esz)) return e;
+  if (int e = check_cfg(cfg, "hiccl_reduce")) return e;
+  hipStream_t s = (hipStream_t)stream;
+  const int dev = current_device();
+  Split sp = split_on(out, count, esz);
+  // engine, shape and store form (write-through by size, as a plan's)
+  Cfg c = oneshot_cfg(dtype, cfg, sp.npkt, (uint64_t)count * esz, n, dev);
+  if (n > kMaxArgInputs) {
+    const std::string why = plan_shape_error(c, dtype);
+    if (!why.empty()) return fail(hipErrorInvalidValue, "hiccl_reduce_ex: n > 64 inputs run on the plan kernel: " + why);
+    // the > 64-input pointer table is uploaded from host memory per call: a
+    // captured graph would replay a copy from a freed host buffer
+    if (capturing(s, false))
+      return fail(hipErrorStreamCaptureUnsupported,
+                  "hiccl_reduce: n > 64 inputs cannot be captured into a graph (use a plan)");
+    return reduce_via_table(dtype, c, out, in, n, count, s);
+  }
+
+  single_fn fn = single_for(dtype, c);
+  if (!fn)
+    return fail(hipErrorInvalidValue, "hiccl_reduce_ex: unsupported config (block " +
+                                          std::to_string(c.block) + ", unroll " +
+                                          std::to_string(c.unroll) + ", nt " +
+                                          std::to_string(c.nt) + ", store " +
+                                          std::to_string(c.store) + ", engine " +
+                                          std::to_string(c.engine) + ") for this dtype");
+
+  SingleArgs a;
+  memset(&a, 0, sizeof(a));
+  a.out = (char *)out;
+  a.npkt = sp.npkt;
+  a.head = sp.head;
+  a.tail = sp.tail;
+  a.n = (uint32_t)n;
+  a.ntiles = tiles_for(sp.npkt, (uint64_t)c.block * c.unroll);
+  for (int k = 0; k < n; k++) a.in[k] = (const char *)in[k];
+
+  const LaunchShape L = launch_shape(c, n, a.ntiles, device_cus(dev));
+  a.grab = L.grab;
+  a.drain = (uint32_t)c.drain;
+  a.order = log2u(c.order);
+  a.sched = L.dynamic ? ticket_counter(dev, s) : nullptr;
+  fn(a, dim3((unsigned)L.grid), s);
+  return check_hip(hipGetLastError(), "hiccl_reduce: launch");
+}
+
+int hiccl_reduce(int dtype, void *out, const void *const *in, int n, size_t count, void *stream) {
+  return hiccl_reduce_ex(dtype, out, in, n, count, stream, nullptr);
+}
+
+int hiccl_reduce_f32(float *out, const float *const *in, int n, size_t count, void *stream) {
+  return hiccl_reduce_ex(HICCL_FLOAT32, out, (const void *const *)in, n, count, stream, nullptr);
+}
+
+int hiccl_reduce_bf16(uint16_t *out, const uint16_t *const *in, int n, size_t count,
+                      void *stream) {
+  return hiccl_reduce_ex(HICCL_BFLOAT16, out, (const void *const *)in, n, count, stream, nullptr);
+}
+
+int hiccl_reduce_auto_choice_ex(int dtype, const hiccl_reduce_config_t *cfg, size_t count, double n, int cus,
+                                int *engine, int *unroll, int *blocks_per_cu, int *dynamic, int *store_policy) {
+  const size_t esz = esize(dtype);
+  if (!esz) return fail(hipErrorInvalidValue, "auto_choice: unknown dtype");
+  if (cus <= 0 || n < 0) return fail(hipErrorInvalidValue, "auto_choice: cus must be > 0 and n >= 0");
+  if (int e = check_cfg(cfg, "auto_choice")) return e;
+  CusOverride scoped(cus);  // no device query: the choice for `cus` CUs
+  const uint64_t npkt = (uint64_t)count * esz / kPacket;
+  const Cfg c = oneshot_cfg(dtype, cfg, npkt, (uint64_t)count * esz, n, -1);
+  // the same refusals as hiccl_reduce_ex: a shape no kernel has is an error
+  const bool has = n > kMaxArgInputs ? plan_shape_error(c, dtype).empty() : single_for(dtype, c) != nullptr;
+  if (!has) return fail(hipErrorInvalidValue, "auto_choice: no kernel for this config and dtype");
+  const uint64_t units = tiles_for(npkt, (uint64_t)c.block * c.unroll);  // tiles or phased chunks
+  const LaunchShape L = launch_shape(c, n, units, cus);
+  if (engine) *engine = c.engine;
+  if (unroll) *unroll = c.unroll;
+  if (blocks_per_cu) *blocks_per_cu = c.bpc;
+  if (dynamic) *dynamic = L.dynamic ? 1 : 0;
+  if (store_policy) *store_policy = c.store + 1;
+  return 0;
+}
+
+int hiccl_reduce_auto_choice(int dtype, int acc, size_t count, double n, int cus, int *engine, int *unroll,
+                             int *blocks_per_cu, int *dynamic) {
+  hiccl_reduce_config_t z;
+  memset(&z, 0, sizeof(z));
+  z.acc = acc;
+  return hiccl_reduce_auto_choice_ex(dtype, &z, count, n, cus, engine, unroll, blocks_per_cu, dynamic, nullptr);
+}
+
+}  // extern "C"

@@ -1,0 +1,341 @@
+// hiccl_amd/csrc/plan.cpp -- hiccl_reduce_plan_*: every compute of a pipeline
+// step in one launch from a device descriptor table.
+#include "plan.h"
+
+#include <string.h>
+
+using namespace hiccl_impl;
+
+namespace hiccl_impl {
+
+void DescTable::add(void *out, const void *const *in, size_t n, size_t count, size_t esz, uint32_t flags) {
+  const Split sp = split_on(out, count, esz);
+  PlanDesc d;
+  d.out = (char *)out;
+  d.npkt = sp.npkt;
+  d.tile_begin = units;
+  d.n = (uint32_t)n;
+  d.head = sp.head;
+  d.tail = sp.tail;
+  d.pad = flags;
+  desc.push_back(d);
+  for (size_t k = 0; k < stride; k++) ptrs.push_back(k < n ? in[k] : nullptr);
+  units += tiles_for(sp.npkt, unit);
+}
+
+std::vector<char> DescTable::image(size_t extra) const {
+  std::vector<char> host(bytes() + extra, 0);
+  if (!desc.empty()) {
+    memcpy(host.data(), desc.data(), ptrs_off());
+    memcpy(host.data() + ptrs_off(), ptrs.data(), ptrs.size() * sizeof(void *));
+  }
+  if (desc.size() > 1) {
+    uint32_t *uc = (uint32_t *)(host.data() + unit_comp_off());
+    for (size_t c = 0; c < desc.size(); c++) {
+      const uint64_t end = c + 1 < desc.size() ? desc[c + 1].tile_begin : units;
+      for (uint64_t t = desc[c].tile_begin; t < end; t++) uc[t] = (uint32_t)c;
+    }
+  }
+  return host;
+}
+
+bool sync_if_enqueued(std::atomic<bool> &enqueued) {
+  if (!enqueued.load(std::memory_order_relaxed)) return false;
+  (void)hipDeviceSynchronize();
+  enqueued.store(false, std::memory_order_relaxed);
+  return true;
+}
+
+int launch_plan(PlanArgs a, int dtype, const Cfg &c, double mean_n, int dev, hipStream_t s, int pol) {
+  plan_fn fn = pick_plan(dtype, c.acc, c.engine, c.unroll, pol);
+  if (!fn)
+    return fail(hipErrorInvalidValue, pol == kDefPol ? "plan: unsupported dtype / shape"
+                                                     : "plan: no peer-policy kernel for this shape (PHASE default, "
+                                                       "TILE unroll 4, f32 / bf16 also 2)");
+  const LaunchShape L = launch_shape(c, mean_n, a.t_end - a.t_begin, device_cus(dev));
+  a.grab = L.grab;
+  a.sched = L.dynamic ? ticket_counter(dev, s) : nullptr;
+  fn(a, dim3((unsigned)L.grid), s);
+  return check_hip(hipGetLastError(), "plan: launch");
+}
+
+// Store form of a plan's launches (see wt_by_size): write-through on request
+// (store_policy 4) or by the bytes a launch writes and its packet-weighted
+// inputs per output.
+static int plan_store_peer(const hiccl_reduce_plan *p) {
+  if (p->req.store_policy == kPolStoreSys + 1) return HICCL_PEER_STORES;
+  uint64_t out = 0;
+  double weighted_n = 0;
+  for (auto &c : p->comps) {
+    out += (uint64_t)c.count * p->esz;
+    weighted_n += (double)c.count * (double)c.in.size();
+  }
+  const double n = out ? weighted_n * (double)p->esz / (double)out : 0.0;
+  return wt_by_size(resolve(&p->req), p->dtype, n, out) ? HICCL_PEER_STORES : 0;
+}
+
+int plan_eff_peer(const hiccl_reduce_plan *p) { return p->peer | plan_store_peer(p); }
+
+}  // namespace hiccl_impl
+
+namespace {
+
+// Before the plan's device block is freed: no launch may still read it.
+void plan_quiesce(hiccl_reduce_plan *p) {
+  if (!sync_if_enqueued(p->enqueued) && p->launched) (void)hipStreamSynchronize(p->last);
+}
+
+// The plan's configuration with its engine and shape resolved for `npkt`
+// packets of packet-weighted mean `mean_n` inputs.
+Cfg plan_cfg(const hiccl_reduce_plan *p, uint64_t npkt, double mean_n) {
+  Cfg c = resolve(&p->req);
+  const bool auto_unroll = !c.unroll;
+  // AUTO's engine rules follow the store form the launches take by size
+  c.wt = c.store_auto && plan_store_peer(p);
+  finish_cfg(c, npkt, mean_n, p->dtype, p->device);
+  // peer and write-through policies: wide tiles become U = 4
+  if (p->eff_peer && c.engine == HICCL_ENGINE_TILE && auto_unroll && !wt_unroll(c.unroll)) c.unroll = kDefUnroll;
+  return c;
+}
+
+int plan_upload(hiccl_reduce_plan *p, hipStream_t s) {
+  if (!p->dirty) return 0;
+  // synchronous allocation + copy: not allowed inside a stream capture
+  // (capture a plan only after a launch outside the capture uploaded it)
+  if (capturing(s, false))
+    return fail(hipErrorStreamCaptureUnsupported,
+                "plan: the first launch after an add or a config change uploads the plan and cannot be captured");
+  if (p->d_block) {
+    plan_quiesce(p);  // a running launch still reads it
+    (void)hipFree(p->d_block);
+    p->d_block = nullptr;
+  }
+  uint64_t total_pkt = 0;
+  double weighted_n = 0;
+  size_t maxn = 0;
+  for (auto &c : p->comps) {
+    const uint64_t k = split_on(c.out, c.count, p->esz).npkt;
+    total_pkt += k;
+    weighted_n += (double)k * c.in.size();
+    if (c.in.size() > maxn) maxn = c.in.size();
+  }
+  p->mean_n = total_pkt ? weighted_n / total_pkt : 0;
+  p->eff_peer = plan_eff_peer(p);
+  const Cfg c = plan_cfg(p, total_pkt, p->mean_n);
+  p->engine = c.engine;
+  p->unroll = c.unroll;
+  p->bpc = c.bpc;
+  DescTable t(maxn, unit_pkts(p->engine, p->dtype, c.acc, p->unroll));
+  for (auto &cp : p->comps) t.add(cp.out, cp.in.data(), cp.in.size(), cp.count, p->esz);
+  const std::vector<char> host = t.image();
+  if (int e = check_hip(hipMalloc((void **)&p->d_block, host.size()), "plan: hipMalloc")) return e;
+  if (int e = check_hip(hipMemcpy(p->d_block, host.data(), host.size(), hipMemcpyHostToDevice), "plan: upload"))
+    return e;
+  memset(&p->args, 0, sizeof(p->args));
+  t.bind(p->args, p->d_block);
+  p->args.t_begin = 0;
+  p->args.t_end = t.units;
+  p->dirty = false;
+  return 0;
+}
+
+int plan_kernel(hiccl_reduce_plan *p, hipStream_t s) {
+  Cfg c = resolve(&p->req);
+  c.engine = p->engine;
+  c.unroll = p->unroll;
+  c.block = p->engine == HICCL_ENGINE_PHASE ? kPhBlock : kDefBlock;
+  c.bpc = p->bpc;
+  return launch_plan(p->args, p->dtype, c, p->mean_n, p->device, s, plan_pol(p->eff_peer));
+}
+
+// Upload (if needed) and launch, no bookkeeping of where the launch went.
+int plan_enqueue_impl(hiccl_reduce_plan_t *p, hipStream_t s, const char *what) {
+  if (!p) return fail(hipErrorInvalidValue, std::string(what) + ": plan is NULL");
+  if (int e = check_hip(hipSetDevice(p->device), (std::string(what) + ": hipSetDevice").c_str())) return e;
+  if (p->comps.empty()) return 0;
+  if (int e = plan_upload(p, s)) return e;
+  return plan_kernel(p, s);
+}
+
+// One field of the plan's config changed: validate the whole, then keep it.
+int plan_set_field(hiccl_reduce_plan_t *p, int hiccl_reduce_config_t::*field, int value, const char *who) {
+  if (!p) return fail(hipErrorInvalidValue, std::string(who) + ": plan is NULL");
+  hiccl_reduce_config_t c = p->req;
+  c.*field = value;
+  if (int e = check_cfg(&c, who)) return e;
+  p->req = c;
+  p->dirty = true;  // (the auto engine's chunk size depends on the accumulator, too)
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int hiccl_reduce_plan_create(hiccl_reduce_plan_t **plan, int dtype, int device) {
+  if (!plan) return fail(hipErrorInvalidValue, "plan_create: plan is NULL");
+  *plan = nullptr;
+  if (!esize(dtype)) return fail(hipErrorInvalidValue, "plan_create: unknown dtype");
+  int ndev = 0;
+  if (int e = check_hip(hipGetDeviceCount(&ndev), "plan_create: hipGetDeviceCount")) return e;
+  if (device < 0 || device >= ndev) return fail(hipErrorInvalidDevice, "plan_create: bad device");
+  if (int e = check_hip(hipSetDevice(device), "plan_create: hipSetDevice")) return e;
+  auto *p = new hiccl_reduce_plan;
+  memset(&p->req, 0, sizeof(p->req));
+  p->dtype = dtype;
+  p->device = device;
+  p->esz = esize(dtype);
+  // the plan's own stream is created on first request (hiccl_reduce_plan_stream):
+  // callers that launch on a shared stream never pay for one
+  *plan = p;
+  return 0;
+}
+
+int hiccl_reduce_plan_set_acc(hiccl_reduce_plan_t *p, int acc) {
+  return plan_set_field(p, &hiccl_reduce_config_t::acc, acc, "plan_set_acc");
+}
+
+int hiccl_reduce_plan_set_engine(hiccl_reduce_plan_t *p, int engine) {
+  return plan_set_field(p, &hiccl_reduce_config_t::engine, engine, "plan_set_engine");
+}
+
+int hiccl_reduce_plan_set_peer(hiccl_reduce_plan_t *p, int flags) {
+  if (!p) return fail(hipErrorInvalidValue, "plan_set_peer: plan is NULL");
+  if (flags & ~(HICCL_PEER_STORES | HICCL_PEER_LOADS))
+    return fail(hipErrorInvalidValue, "plan_set_peer: flags must be a combination of HICCL_PEER_STORES and HICCL_PEER_LOADS");
+  p->peer = flags;
+  p->dirty = true;
+  return 0;
+}
+
+int hiccl_reduce_plan_peer(const hiccl_reduce_plan_t *p) { return p ? p->peer : -1; }
+
+int hiccl_reduce_plan_store_policy(const hiccl_reduce_plan_t *p) {
+  if (!p) return -1;
+  return (plan_eff_peer(p) & HICCL_PEER_STORES) ? kPolStoreSys + 1 : kDefPol / 10 + 1;
+}
+
+int hiccl_reduce_plan_set_config(hiccl_reduce_plan_t *p, const hiccl_reduce_config_t *cfg) {
+  if (!p) return fail(hipErrorInvalidValue, "plan_set_config: plan is NULL");
+  hiccl_reduce_config_t z;
+  memset(&z, 0, sizeof(z));
+  const hiccl_reduce_config_t &c = cfg ? *cfg : z;
+  if (int e = check_cfg(&c, "plan_set_config")) return e;
+  // the shape must be one the plan kernels have, whatever engine AUTO picks
+  Cfg r = resolve(&c);
+  const bool shape = c.block || c.unroll;
+  if (shape && r.engine == HICCL_ENGINE_AUTO) r.engine = HICCL_ENGINE_TILE;
+  const int engines[2] = {HICCL_ENGINE_TILE, HICCL_ENGINE_PHASE};
+  for (int eng : engines) {
+    if (r.engine != HICCL_ENGINE_AUTO && r.engine != eng) continue;
+    Cfg t = r;
+    t.engine = eng;
+    if (!t.block) t.block = eng == HICCL_ENGINE_PHASE ? kPhBlock : kDefBlock;
+    if (!t.unroll) t.unroll = eng == HICCL_ENGINE_PHASE ? phase_p(p->dtype, t.acc) : kDefUnroll;
+    const std::string why = plan_shape_error(t, p->dtype);
+    if (!why.empty()) return fail(hipErrorInvalidValue, "plan_set_config: " + why);
+  }
+  p->req = c;
+  p->dirty = true;
+  return 0;
+}
+
+int hiccl_reduce_plan_engine(const hiccl_reduce_plan_t *p) { return p ? p->engine : -1; }
+
+int hiccl_reduce_plan_add(hiccl_reduce_plan_t *p, void *out, const void *const *in, int n,
+                          size_t count) {
+  if (!p) return fail(hipErrorInvalidValue, "plan_add: plan is NULL");
+  if (p->dtype == HICCL_BYTES && n != 1) return fail(hipErrorInvalidValue, "plan_add: HICCL_BYTES copies need n == 1");
+  if (int e = check_buffers(out, in, n, count, p->esz)) return e;
+  if (count == 0) return 0;
+  hiccl_reduce_plan::Comp c;
+  c.out = out;
+  c.in.assign(in, in + n);
+  c.count = count;
+  p->comps.push_back(std::move(c));
+  p->dirty = true;
+  return 0;
+}
+
+int hiccl_reduce_plan_enqueue(hiccl_reduce_plan_t *p, void *stream) {
+  if (int e = plan_enqueue_impl(p, (hipStream_t)stream, "plan_enqueue")) return e;
+  // no stream bookkeeping (callers on several threads and streams); a
+  // re-upload or destroy then synchronises the device before it frees the
+  // block a launch may still read
+  if (!p->comps.empty()) p->enqueued.store(true, std::memory_order_relaxed);
+  return 0;
+}
+
+int hiccl_reduce_plan_launch(hiccl_reduce_plan_t *p, void *stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (int e = plan_enqueue_impl(p, s, "plan_launch")) return e;
+  if (p->comps.empty()) return 0;
+  // a capturing stream is not remembered (plan_sync does not apply to graph
+  // replays: synchronise the stream the graph runs on); a re-upload or
+  // destroy of a plan captured into a graph synchronises the device
+  if (capturing(s, false)) {
+    p->enqueued.store(true, std::memory_order_relaxed);
+    return 0;
+  }
+  p->launched = true;
+  p->last = s;
+  return 0;
+}
+
+int hiccl_reduce_plan_launch_each(hiccl_reduce_plan_t *p, void *stream) {
+  if (!p) return fail(hipErrorInvalidValue, "plan_launch_each: plan is NULL");
+  if (int e = check_hip(hipSetDevice(p->device), "plan_launch_each: hipSetDevice")) return e;
+  if (p->comps.empty()) return 0;
+  // One one-shot launch per compute, each with the engine AUTO picks for that
+  // compute alone (the reference's structure, compute.h:88-91).
+  for (auto &c : p->comps)
+    if (int e = hiccl_reduce_ex(p->dtype, c.out, c.in.data(), (int)c.in.size(), c.count, stream, &p->req))
+      return e;
+  p->launched = true;
+  p->last = (hipStream_t)stream;
+  return 0;
+}
+
+int hiccl_reduce_plan_sync(hiccl_reduce_plan_t *p) {
+  if (!p) return fail(hipErrorInvalidValue, "plan_sync: plan is NULL");
+  if (!p->launched) return 0;
+  if (int e = check_hip(hipSetDevice(p->device), "plan_sync: hipSetDevice")) return e;
+  // the reference's wait(): hipStreamSynchronize of the compute's stream
+  // (compute.h:107-117) -- no completion event per launch (an event record
+  // after every kernel costs the queue ~3 us per step on MI355X)
+  if (int e = check_hip(hipStreamSynchronize(p->last), "plan_sync")) return e;
+  // nothing of this plan is pending on that stream any more: a later
+  // re-upload or destroy does not touch it (the caller may destroy it)
+  p->launched = false;
+  return 0;
+}
+
+int hiccl_reduce_plan_numcomp(const hiccl_reduce_plan_t *p) { return p ? (int)p->comps.size() : 0; }
+
+void *hiccl_reduce_plan_stream(hiccl_reduce_plan_t *p) {
+  if (!p) return nullptr;
+  if (!p->own) {
+    if (check_hip(hipSetDevice(p->device), "plan_stream: hipSetDevice")) return nullptr;
+    if (check_hip(hipStreamCreateWithFlags(&p->own, hipStreamNonBlocking), "plan_stream: create")) return nullptr;
+  }
+  return (void *)p->own;
+}
+
+size_t hiccl_reduce_plan_bytes(const hiccl_reduce_plan_t *p) {
+  if (!p) return 0;
+  size_t b = 0;
+  for (auto &c : p->comps) b += c.count * (c.in.size() + 1) * p->esz;
+  return b;
+}
+
+void hiccl_reduce_plan_destroy(hiccl_reduce_plan_t *p) {
+  if (!p) return;
+  (void)hipSetDevice(p->device);
+  if (p->d_block) plan_quiesce(p);
+  else if (p->launched) (void)hipStreamSynchronize(p->last);
+  if (p->d_block) (void)hipFree(p->d_block);
+  if (p->own) (void)hipStreamDestroy(p->own);
+  delete p;
+}
+
+}  // extern "C"

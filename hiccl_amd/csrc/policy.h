@@ -1,0 +1,64 @@
+// hiccl_amd/csrc/policy.h -- the launch policy: a caller's config resolved
+// into engine, shape, store form, grid and schedule.  Pure functions of
+// their arguments plus device_cus(); the rules and thresholds: policy.cpp.
+#pragma once
+
+#include <string>
+
+#include "runtime.h"
+
+namespace hiccl_impl __attribute__((visibility("hidden"))) {
+
+struct Cfg {
+  int block, unroll, bpc, nt, acc, grid, store, engine, schedule, grab, drain;
+  bool store_auto;  // store_policy 0: the store form follows the launch's size (wt_by_size)
+  bool wt;          // the launch stores write-through by size: decided BEFORE the engine
+                    // (oneshot_cfg, plan_cfg), since AUTO's engine rules differ under it
+  int order;        // tile-order segments (hiccl_reduce_config_t.order; 0/1 linear)
+  int pol() const { return store * 10 + nt; }
+};
+
+// Raw config: zero block/unroll stay zero until the engine is known.
+Cfg resolve(const hiccl_reduce_config_t *c);
+
+// The enumerated and ranged fields of a caller's config (NULL: all
+// defaults), refused as `who: ...` with hipErrorInvalidValue.
+int check_cfg(const hiccl_reduce_config_t *c, const std::string &who);
+
+// Does a launch that writes `out_bytes` from `n` inputs per output (a plan's
+// packet-weighted mean) store write-through BY SIZE under the raw config?
+bool wt_by_size(const Cfg &raw, int dtype, double n, uint64_t out_bytes);
+// Write-through (and peer-policy) TILE launches run at these unrolls.
+inline bool wt_unroll(int unroll) { return unroll == 2 || unroll == kDefUnroll; }
+
+// Fill in the engine and its default shape (n: inputs, or a plan's
+// packet-weighted mean).
+void finish_cfg(Cfg &c, uint64_t npkt, double n, int dtype, int dev);
+
+// The one-shot call's configuration, engine and store form resolved.
+Cfg oneshot_cfg(int dtype, const hiccl_reduce_config_t *cfg, uint64_t npkt, uint64_t out_bytes, double n, int dev);
+// Its kernel (n <= kMaxArgInputs), or NULL.
+inline single_fn single_for(int dtype, const Cfg &c) {
+  return pick_single(dtype, c.acc, c.engine, c.block, c.unroll, c.pol());
+}
+
+// The plan kernels' cache policy: nt loads and stores, or a plan's peer
+// policy (HICCL_PEER_* flags: system-scope stores and/or loads).
+int plan_pol(int peer);
+// Packets per work unit (tile or chunk) of a plan kernel.
+uint64_t unit_pkts(int engine, int dtype, int acc, int unroll);
+// Is `c` (engine resolved, shape filled in by finish_cfg) a shape the plan
+// kernels have?  Empty string if so, else why not.
+std::string plan_shape_error(const Cfg &c, int dtype);
+
+// The shape of one launch of `units` work units of `n` inputs (mean) on a
+// device of `cus` CUs: workgroups, units per ticket, and whether the units
+// are handed out by a ticket counter (dynamic) or grid-stride.
+struct LaunchShape {
+  uint64_t grid;
+  uint32_t grab;
+  bool dynamic;
+};
+LaunchShape launch_shape(const Cfg &c, double n, uint64_t units, int cus);
+
+}  // namespace hiccl_impl

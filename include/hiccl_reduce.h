@@ -16,7 +16,7 @@
  * arguments return hipErrorInvalidValue (1) and leave a message readable with
  * hiccl_last_error().
  *
- * Implementation: hiccl_amd/csrc/reduce.hip -> hiccl_amd/libhiccl_reduce.so
+ * Implementation: hiccl_amd/csrc/ (kernels: reduce.hip) -> hiccl_amd/libhiccl_reduce.so
  * Design and roofline: DESIGN.md.  Reference-side bindings: INTEGRATION.md.
  */
 #ifndef HICCL_REDUCE_H

@@ -10,7 +10,7 @@ spent (the GPU tier kept its own copy of the rule and
 went red after two rule changes).
 
 Rule: DESIGN.md section 4 (AUTO table, store form by launch size);
-hiccl_amd/csrc/reduce.hip auto_engine / oneshot_cfg / plan_store_peer.
+hiccl_amd/csrc/policy.cpp auto_engine / oneshot_cfg / wt_by_size.
 """
 import hiccl_amd._lib as L
 

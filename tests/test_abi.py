@@ -26,6 +26,16 @@ def test_exports_every_header_symbol():
     assert not [n for n in names if n not in L._SIGS]
 
 
+def test_exports_nothing_but_the_header_functions():
+    """The library's defined strong text symbols are exactly the functions
+    include/hiccl_reduce.h declares: what the host files share with each
+    other and with the kernel file stays internal."""
+    import subprocess
+    out = subprocess.run(["nm", "-D", "--defined-only", L.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    strong = sorted(line.split()[2] for line in out.splitlines() if len(line.split()) == 3 and line.split()[1] == "T")
+    assert strong == L.header_functions()
+
+
 def test_gfx950_code_object_embedded():
     blob = open(L.LIB_PATH, "rb").read()
     assert b"gfx950" in blob
