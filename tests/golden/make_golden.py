@@ -5,7 +5,11 @@ TEST INFRASTRUCTURE.  Run in the build container (where /root/reference
 exists):
 
     make -C oracle            # liboracle.so + _ref/libhiccl_ref.so
-    python tests/golden/make_golden.py
+    python tests/golden/make_golden.py [--only reduce_bf16 ...]
+
+(`--only NAME` rewrites the named fixture sets and their manifest entries and
+leaves the other files as committed: an .npz written again differs in its
+zip timestamps, hence in its sha256, with the same arrays inside.)
 
 Expected outputs come from the REFERENCE ITSELF: HiCCL's CPU
 ``reduce_kernel<T>`` (source/compute.h:14-23), compiled unmodified from the
@@ -23,6 +27,7 @@ Each fixture file is an .npz of plain numeric arrays (no pickles):
 plus manifest.json with per-file sha256, the generator parameters and which
 library produced the expected outputs.
 """
+import argparse
 import ctypes
 import hashlib
 import json
@@ -126,6 +131,28 @@ def f32_to_bf16_bits(x):
     return r
 
 
+def special_bf16():
+    """The f32 table rounded to bf16 (its denormal columns become 0 there),
+    then columns only bf16 bit patterns can state: true bf16 subnormals (unit
+    2^-133 = 0x0001; the smallest normal is 0x0080) as inputs and as results,
+    and the round-to-Inf tie -- the largest bf16 (0x7F7F) plus half its ulp
+    (2^119 = 0x7B00): the f32 sum is exact and the conversion ties to even,
+    which is Inf."""
+    sp = f32_to_bf16_bits(special_f32())
+    extra = [
+        (0x0001, 0x0001, 0x8001),    # subnormal arithmetic, no flush
+        (0x0003, 0x8001, 0x0007),
+        (0x8005, 0x0002, 0x0000),    # a negative subnormal result
+        (0x0080, 0x8003, 0x0000),    # smallest normal - 3 units: drops into the subnormal range
+        (0x007F, 0x0001, 0x0000),    # largest subnormal + 1 unit: the smallest normal
+        (0x0040, 0x0040, 0x0040),
+        (0x7F7F, 0x7B00, 0x0000),    # max + half an ulp: ties to even = Inf
+        (0xFF7F, 0xFB00, 0x7B00),    # -max - half an ulp = -Inf, which stays
+        (0x7F7F, 0x7A80, 0x0000),    # max + a quarter ulp: stays max
+    ]
+    return np.concatenate([sp, np.array(extra, dtype=np.uint16).T], axis=1)
+
+
 def sha(path):
     h = hashlib.sha256()
     with open(path, "rb") as fh:
@@ -133,13 +160,23 @@ def sha(path):
     return h.hexdigest()
 
 
-def main():
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument("--only", nargs="+", metavar="NAME", help="fixture sets to rewrite (e.g. reduce_bf16); default all")
+    only = ap.parse_args(argv).only
     ref, ref16, ora = load_libs()
     rng = np.random.default_rng(SEED)
     manifest = {"seed": SEED, "generator": "tests/golden/make_golden.py",
                 "reference": "source/compute.h:14-23 reduce_kernel<T> (oracle/_ref/libhiccl_ref.so; bf16: "
                              "reduce_kernel<__hip_bfloat16>, oracle/_ref/libhiccl_ref_bf16.so)",
                 "files": {}}
+    if only:
+        with open(os.path.join(HERE, "manifest.json")) as fh:
+            manifest["files"] = json.load(fh)["files"]
+
+    def write(name, cases, pinned_by):
+        if not only or name in only:
+            save(name, cases, manifest, pinned_by)
 
     def check(name, dtype, ref_fn, ora_fn, inputs, count):
         exp = run(ref16 if ref_fn == "ref_reduce_bf16" else ref, ref_fn, dtype, inputs, count)
@@ -173,7 +210,7 @@ def main():
                                      list(x1), x.shape[1]))
     x0 = np.zeros((0, 5), np.float32)
     cases["empty_n0_c5"] = (x0, check("n0", np.float32, "ref_reduce_f32", "oracle_reduce_f32", [], 5))
-    save("reduce_f32", cases, manifest, "reference")
+    write("reduce_f32", cases, "reference")
 
     # ---- f64
     cases = {}
@@ -182,7 +219,7 @@ def main():
             x = rng.uniform(-1, 1, size=(n, c)).astype(np.float64) * np.exp2(rng.integers(-60, 60, size=(n, c)))
             cases[f"rand_n{n}_c{c}"] = (x, check("f64", np.float64, "ref_reduce_f64", "oracle_reduce_f64",
                                                   list(x), c))
-    save("reduce_f64", cases, manifest, "reference")
+    write("reduce_f64", cases, "reference")
 
     # ---- size_t: the reference's own known-answer pattern (bench.h:80-82:
     # sendbuf[i] = i; rank p contributes element p*count + i), and wrap-around.
@@ -193,7 +230,7 @@ def main():
         cases[f"kat_n{n}"] = (x, check("u64", np.uint64, "ref_reduce_u64", "oracle_reduce_u64", list(x), c))
     x = rng.integers(0, 2**64 - 1, size=(4, 1031), dtype=np.uint64)
     cases["wrap_n4"] = (x, check("u64wrap", np.uint64, "ref_reduce_u64", "oracle_reduce_u64", list(x), 1031))
-    save("reduce_u64", cases, manifest, "reference")
+    write("reduce_u64", cases, "reference")
 
     # ---- int32: small values, and full-range values whose sums wrap
     cases = {}
@@ -202,7 +239,7 @@ def main():
         cases[f"small_n{n}"] = (x, check("i32", np.int32, "ref_reduce_i32", "oracle_reduce_i32", list(x), 4099))
     x = rng.integers(-2**31, 2**31, size=(5, 1031), dtype=np.int64).astype(np.int32)
     cases["wrap_n5"] = (x, check("i32wrap", np.int32, "ref_reduce_i32", "oracle_reduce_i32", list(x), 1031))
-    save("reduce_i32", cases, manifest, "reference")
+    write("reduce_i32", cases, "reference")
 
     # ---- bf16: reduce_kernel<__hip_bfloat16>
     cases = {}
@@ -212,14 +249,14 @@ def main():
             x = f32_to_bf16_bits(xf * np.float32(n))  # spread magnitudes a little
             cases[f"rand_n{n}_c{c}"] = (x, check("bf16", np.uint16, "ref_reduce_bf16", "oracle_reduce_bf16",
                                                   list(x), c))
-    sp = f32_to_bf16_bits(special_f32())
+    sp = special_bf16()
     cases["special_n3"] = (sp, check("bf16sp", np.uint16, "ref_reduce_bf16", "oracle_reduce_bf16", list(sp),
                                         sp.shape[1]))
-    save("reduce_bf16", cases, manifest, "reference")
+    write("reduce_bf16", cases, "reference")
 
     with open(os.path.join(HERE, "manifest.json"), "w") as fh:
         json.dump(manifest, fh, indent=1, sort_keys=True)
-    print("wrote", sorted(manifest["files"]))
+    print("wrote", sorted(f for f in manifest["files"] if not only or f.split(".")[0] in only))
 
 
 PART_BYTES = 768 << 10  # arrays per fixture file: every committed file stays under 1 MiB
@@ -237,6 +274,8 @@ def save(name, cases, manifest, pinned_by):
         parts[-1][f"{k}/in"] = x
         parts[-1][f"{k}/out"] = y
         size += x.nbytes + y.nbytes
+    for fname in [f for f in manifest["files"] if f == f"{name}.npz" or f.startswith(f"{name}.part")]:
+        del manifest["files"][fname]  # (a set written again may take fewer files)
     for i, arrs in enumerate(parts):
         fname = f"{name}.npz" if i == 0 else f"{name}.part{i + 1}.npz"
         path = os.path.join(HERE, fname)
