@@ -95,11 +95,14 @@ int hiccl_reduce_ex(int dtype, void *out, const void *const *in, int n, size_t c
   a.ntiles = tiles_for(sp.npkt, (uint64_t)c.block * c.unroll);
   for (int k = 0; k < n; k++) a.in[k] = (const char *)in[k];
 
-  const LaunchShape L = launch_shape(c, n, a.ntiles, device_cus(dev));
+  LaunchShape L = launch_shape(c, n, a.ntiles, device_cus(dev), /*paced=*/true);
+  a.sched = L.dynamic ? ticket_counter(dev, s) : nullptr;
+  // no counter for this stream (capture, hipStreamPerThread): the launch runs
+  // static and unpaced, on the full grid
+  if (L.dynamic && !a.sched) L = launch_shape(c, n, a.ntiles, device_cus(dev));
   a.grab = L.grab;
   a.drain = (uint32_t)c.drain;
   a.order = log2u(c.order);
-  a.sched = L.dynamic ? ticket_counter(dev, s) : nullptr;
   fn(a, dim3((unsigned)L.grid), s);
   return check_hip(hipGetLastError(), "hiccl_reduce: launch");
 }
@@ -130,7 +133,7 @@ int hiccl_reduce_auto_choice_ex(int dtype, const hiccl_reduce_config_t *cfg, siz
   const bool has = n > kMaxArgInputs ? plan_shape_error(c, dtype).empty() : single_for(dtype, c) != nullptr;
   if (!has) return fail(hipErrorInvalidValue, "auto_choice: no kernel for this config and dtype");
   const uint64_t units = tiles_for(npkt, (uint64_t)c.block * c.unroll);  // tiles or phased chunks
-  const LaunchShape L = launch_shape(c, n, units, cus);
+  const LaunchShape L = launch_shape(c, n, units, cus, /*paced=*/n <= kMaxArgInputs);
   if (engine) *engine = c.engine;
   if (unroll) *unroll = c.unroll;
   if (blocks_per_cu) *blocks_per_cu = c.bpc;

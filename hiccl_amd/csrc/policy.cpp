@@ -40,6 +40,9 @@ constexpr uint64_t kWtMaxBytes = 32ull << 20;
 constexpr uint64_t kWtMaxBytesReduce = 256ull << 20;
 inline uint64_t wt_cap(double n) { return n >= 1.5 ? kWtMaxBytesReduce : kWtMaxBytes; }
 
+// The paced one-shot tiles' share of the default grid (launch_shape).
+constexpr uint64_t kPacedGridNum = 7, kPacedGridDen = 8;
+
 constexpr int kDefBpc = 1;
 constexpr int kSmallBpc = 4;
 // auto engine: with >= 5 inputs the TILE engine on the dynamic schedule;
@@ -296,7 +299,18 @@ std::string plan_shape_error(const Cfg &c, int dtype) {
 // addresses mod grid x 16 KiB, i.e. to a fixed subset of DRAM channels, and
 // the ones on slow channels straggle: 5.6-5.7 vs 6.3-6.7 TB/s on C2), and
 // only from kDynMinUnitsPerWG tickets per workgroup.
-LaunchShape launch_shape(const Cfg &c, double n, uint64_t units, int cus) {
+//
+// `paced`: the launch runs the one-shot kernel, whose dynamic tiles pace
+// their load burst (reduce.hip group_at).  Such a launch takes 7 of every 8
+// workgroups of the default grid (28 of an XCD's 32 CUs): config 2 in fresh
+// processes, alternating rounds, 1.402 ms at 224 workgroups against 1.445 at
+// 256, 1.418 / 1.406 at 240 / 232 and 1.402 / 1.407 / 1.418 at 216 / 208 /
+// 200; the unpaced kernels gained 0.5-0.8 % from the same step (waterfall
+// loops 1.435 vs 1.441, scalar descriptors 1.445 vs 1.457;
+// profiles/r07a_pace_ab.jsonl, r07a_grid_ab.jsonl).  Whether the schedule is dynamic is decided on the
+// full grid, so the rule moves no launch between the schedules; a grid the
+// caller names is kept.
+LaunchShape launch_shape(const Cfg &c, double n, uint64_t units, int cus, bool paced) {
   LaunchShape L;
   L.grid = c.grid > 0 ? (uint64_t)c.grid : (uint64_t)cus * c.bpc;
   if (L.grid > units) L.grid = units;
@@ -304,6 +318,8 @@ LaunchShape launch_shape(const Cfg &c, double n, uint64_t units, int cus) {
   const bool auto_static = c.engine != HICCL_ENGINE_TILE || (n < kDynMinInputs && c.unroll < kWideUnroll);
   L.dynamic = c.schedule != HICCL_SCHED_STATIC && !(c.schedule == HICCL_SCHED_AUTO && auto_static) &&
               (units + L.grab - 1) / L.grab >= kDynMinUnitsPerWG * L.grid;
+  if (paced && L.dynamic && c.engine == HICCL_ENGINE_TILE && c.grid <= 0 && L.grid >= 8)
+    L.grid = L.grid * kPacedGridNum / kPacedGridDen;
   return L;
 }
 

@@ -59,6 +59,8 @@ struct LaunchShape {
   uint32_t grab;
   bool dynamic;
 };
-LaunchShape launch_shape(const Cfg &c, double n, uint64_t units, int cus);
+// `paced`: a launch of the one-shot kernel (its dynamic tiles pace their loads
+// and take 7/8 of the default grid).
+LaunchShape launch_shape(const Cfg &c, double n, uint64_t units, int cus, bool paced = false);
 
 }  // namespace hiccl_impl

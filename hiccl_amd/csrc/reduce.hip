@@ -282,7 +282,21 @@ __device__ __forceinline__ void scalar_part(char *out, Inputs in, uint32_t n, ui
 
 // One group of G inputs (G static): G descriptor builds (scalar), then G*U
 // independent 16-B buffer loads, then the G in-order adds per packet.
-template <class Op, int U, int G, int POL, class Inputs>
+//
+// PACED: a pause of kPaceSleep x 64 clocks between one input's U loads and the
+// next input's.  With scalar descriptors the G*U loads of a wave issue back to
+// back, and on the one launch that is bound by HBM alone -- config 2's
+// one-shot tiles on the ticket counter, 256 workgroups x 4 waves bursting 32
+// KiB each -- that burst measured 1.1-1.6 % SLOWER than the waterfall loops
+// it replaced, which had spread the same loads over about a microsecond.
+// Spreading them on purpose gives that back, and on 7/8 of the grid
+// (policy.cpp launch_shape) runs 2.4 % ahead.  The
+// pauses hide under the tile's memory time; a latency-bound launch (static
+// schedule, plans, programs) would pay for them, so only the one-shot
+// kernel's dynamic schedule asks for them.
+constexpr int kPaceSleep = 4;
+
+template <class Op, int U, int G, int POL, bool PACED, class Inputs>
 __device__ __forceinline__ void group_at(typename Op::acc_t (&acc)[U], Inputs in, uint32_t g,
                                          uint64_t tile_off, uint32_t tile_bytes,
                                          const uint32_t (&voff)[U]) {
@@ -301,6 +315,12 @@ __device__ __forceinline__ void group_at(typename Op::acc_t (&acc)[U], Inputs in
 #pragma unroll
     for (int u = 0; u < U; u++) x[j][u] = load_pkt<POL>(r[j], voff[u]);
     __builtin_amdgcn_sched_barrier(0);
+    if constexpr (PACED) {
+      if (j + 1 < G) {
+        __builtin_amdgcn_s_sleep(kPaceSleep);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
   }
 #pragma unroll
   for (int j = 0; j < G; j++) {
@@ -317,33 +337,38 @@ __device__ __forceinline__ void group_at(typename Op::acc_t (&acc)[U], Inputs in
 // scheduler publishes its next ticket there: every load has been waited for
 // and no store is pending yet, so reading the atomic's result costs nothing).
 struct NoHook {
+  static constexpr bool kDynamic = false;
   __device__ void operator()() const {}
 };
 
-template <class Op, int U, int POL, class Inputs, class Hook = NoHook>
+template <class Op, int U, int POL, bool PACED = false, class Inputs, class Hook = NoHook>
 __device__ __forceinline__ void tile_body(char *outb, Inputs in, uint32_t n, uint64_t tile_off,
                                           uint32_t tile_bytes, const uint32_t (&voff)[U],
                                           Hook before_store = Hook()) {
   typename Op::acc_t acc[U];
 #pragma unroll
   for (int u = 0; u < U; u++) acc[u] = Op::zero();
+  // The output's descriptor is built here, ahead of the input groups, and not
+  // next to the stores: built behind the switch below, the u64 kernels got it
+  // as a VGPR copy joined over the switch's cases, and with it a waterfall
+  // loop around each of their stores (4 SGPRs held over the tile instead).
+  const rsrc_t w = make_rsrc(outb + tile_off, tile_bytes);
   // groups of GM inputs: at most 32 packets per lane in flight (U = 8: 4
   // inputs, U = 16: 2), so wide tiles stay within the register file
   constexpr uint32_t GM = U >= 8 ? 32 / U : 8;
   uint32_t g = 0;
-  for (; g + GM <= n; g += GM) group_at<Op, U, GM, POL>(acc, in, g, tile_off, tile_bytes, voff);
+  for (; g + GM <= n; g += GM) group_at<Op, U, GM, POL, PACED>(acc, in, g, tile_off, tile_bytes, voff);
   switch (n - g) {  // wave-uniform
-    case 1: group_at<Op, U, 1, POL>(acc, in, g, tile_off, tile_bytes, voff); break;
-    case 2: if constexpr (GM > 2) group_at<Op, U, 2, POL>(acc, in, g, tile_off, tile_bytes, voff); break;
-    case 3: if constexpr (GM > 3) group_at<Op, U, 3, POL>(acc, in, g, tile_off, tile_bytes, voff); break;
-    case 4: if constexpr (GM > 4) group_at<Op, U, 4, POL>(acc, in, g, tile_off, tile_bytes, voff); break;
-    case 5: if constexpr (GM > 5) group_at<Op, U, 5, POL>(acc, in, g, tile_off, tile_bytes, voff); break;
-    case 6: if constexpr (GM > 6) group_at<Op, U, 6, POL>(acc, in, g, tile_off, tile_bytes, voff); break;
-    case 7: if constexpr (GM > 7) group_at<Op, U, 7, POL>(acc, in, g, tile_off, tile_bytes, voff); break;
+    case 1: group_at<Op, U, 1, POL, PACED>(acc, in, g, tile_off, tile_bytes, voff); break;
+    case 2: if constexpr (GM > 2) group_at<Op, U, 2, POL, PACED>(acc, in, g, tile_off, tile_bytes, voff); break;
+    case 3: if constexpr (GM > 3) group_at<Op, U, 3, POL, PACED>(acc, in, g, tile_off, tile_bytes, voff); break;
+    case 4: if constexpr (GM > 4) group_at<Op, U, 4, POL, PACED>(acc, in, g, tile_off, tile_bytes, voff); break;
+    case 5: if constexpr (GM > 5) group_at<Op, U, 5, POL, PACED>(acc, in, g, tile_off, tile_bytes, voff); break;
+    case 6: if constexpr (GM > 6) group_at<Op, U, 6, POL, PACED>(acc, in, g, tile_off, tile_bytes, voff); break;
+    case 7: if constexpr (GM > 7) group_at<Op, U, 7, POL, PACED>(acc, in, g, tile_off, tile_bytes, voff); break;
     default: break;
   }
   before_store();
-  rsrc_t w = make_rsrc(outb + tile_off, tile_bytes);
 #pragma unroll
   for (int u = 0; u < U; u++) store_pkt<POL>(w, voff[u], Op::pack(acc[u]));
 }
@@ -414,13 +439,39 @@ __device__ __forceinline__ void chunk_body(char *outb, Inputs in, uint32_t n, ui
 constexpr int kTile = 0;
 constexpr int kPhase = 1;
 
-template <class Op, int U, int POL, int ENG, class Inputs, class Hook>
+// A value every lane of the workgroup holds alike, moved to SGPRs.
+__device__ __forceinline__ uint32_t uniform32(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ uint64_t uniform64(uint64_t v) {
+  return (uint64_t)uniform32((uint32_t)(v >> 32)) << 32 | uniform32((uint32_t)v);
+}
+
+// One unit of either engine.  Every kernel's units come through here, and
+// this is where a unit's two descriptor inputs -- its byte offset and its
+// valid byte count -- are made scalar, once per unit: the bodies' make_rsrc
+// then add them to kernarg / constant-memory pointers and every descriptor
+// stays in SGPRs.  Left alone they reach the bodies in VGPRs (the unit index
+// comes out of LDS on the dynamic schedule and through tile_order's branch;
+// the byte count out of a 64-bit compare/select, which gfx9 has on the VALU
+// only), and the compiler then wraps EACH buffer load and store in a
+// readfirstlane waterfall loop: ~12 instructions per memory op, one loop
+// finished before the next op issues.
+// Both values are workgroup-uniform on every path: they are functions of the
+// unit index and of kernel arguments / descriptor words read at uniform
+// addresses, and the unit index is blockIdx.x + k * gridDim.x (static
+// schedule, k_program) or a ticket that thread 0 stored to s_next[] before
+// the barrier every lane read it behind (for_each_unit).  tile_order (any
+// `order`) and the clamp of the last, partial unit are pure functions of
+// those; a scalar-only compute returns before it gets here, on a uniform
+// branch.
+template <class Op, int U, int POL, int ENG, bool PACED = false, class Inputs, class Hook = NoHook>
 __device__ __forceinline__ void unit_body(char *outb, Inputs in, uint32_t n, uint64_t off,
-                                          uint32_t nbytes, const uint32_t (&voff)[U], Hook hook) {
+                                          uint32_t nbytes, const uint32_t (&voff)[U], Hook hook = Hook()) {
+  const uint64_t uoff = uniform64(off);
+  const uint32_t ubytes = uniform32(nbytes);
   if constexpr (ENG == kPhase)
-    chunk_body<Op, U, POL>(outb, in, n, off, nbytes, voff, hook);
+    chunk_body<Op, U, POL>(outb, in, n, uoff, ubytes, voff, hook);
   else
-    tile_body<Op, U, POL>(outb, in, n, off, nbytes, voff, hook);
+    tile_body<Op, U, POL, PACED>(outb, in, n, uoff, ubytes, voff, hook);
 }
 
 // Body inputs shifted by the head: base(k) = in[k] + head*esz.
@@ -447,12 +498,21 @@ __device__ __forceinline__ void drain_stores(uint32_t drain) {
   if (drain) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
+// The hook a unit of the dynamic schedule gets.  kDynamic lets a kernel tell
+// the two schedules apart at compile time (NoHook: the static one).
+template <class F>
+struct TicketHook {
+  static constexpr bool kDynamic = true;
+  F f;
+  __device__ void operator()() const { f(); }
+};
+
 template <class Body>
 __device__ __forceinline__ void for_each_unit(uint32_t *sched, uint32_t grab, uint64_t t0, uint64_t t1,
                                               Body body, uint32_t drain = 0) {
   if (!sched) {
     for (uint64_t t = t0 + blockIdx.x; t < t1; t += gridDim.x) {
-      body(t, [] {});
+      body(t, NoHook());
       drain_stores(drain);
     }
     return;
@@ -475,9 +535,10 @@ __device__ __forceinline__ void for_each_unit(uint32_t *sched, uint32_t grab, ui
     const uint64_t tend = (t + grab < t1) ? t + grab : t1;
     for (uint64_t u = t; u < tend; u++) {
       const bool last = u + 1 == tend;
-      body(u, [&]() {
+      auto publish = [&]() {
         if (last && threadIdx.x == 0) s_next[slot] = nxt;
-      });
+      };
+      body(u, TicketHook<decltype(publish)>{publish});
       drain_stores(drain);
     }
     __syncthreads();
@@ -534,7 +595,8 @@ __global__ __launch_bounds__(BLOCK) void k_reduce_single(SingleArgs a) {
     const uint64_t pkt0 = t * TILE;
     const uint64_t left = a.npkt - pkt0;
     const uint32_t tile_bytes = (uint32_t)((left < TILE ? left : TILE) * kPacket);
-    unit_body<Op, U, POL, ENG>(outb, in, a.n, pkt0 * kPacket, tile_bytes, voff, hook);
+    // the dynamic schedule's tiles pace their load burst (group_at)
+    unit_body<Op, U, POL, ENG, decltype(hook)::kDynamic>(outb, in, a.n, pkt0 * kPacket, tile_bytes, voff, hook);
   }, a.drain);
 }
 
@@ -818,7 +880,7 @@ __device__ __forceinline__ void prog_unit_of(const PlanDesc &d, TableInputs raw,
   Shifted<TableInputs> in{raw, shift};
   const uint64_t left = d.npkt - pkt0;
   const uint32_t tile_bytes = (uint32_t)((left < TILE ? left : TILE) * kPacket);
-  tile_body<Op, U, POL>(d.out + shift, in, d.n, pkt0 * kPacket, tile_bytes, voff);
+  unit_body<Op, U, POL, kTile>(d.out + shift, in, d.n, pkt0 * kPacket, tile_bytes, voff);
 }
 
 // A unit under its compute's peer policy (the plan's hiccl_reduce_plan_set_peer
