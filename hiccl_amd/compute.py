@@ -136,7 +136,9 @@ class Compute:
     add(inputbuf, outputbuf, count, compid)  compute.h:47-85 -- records the
         compute only when ``myid == compid`` (SPMD: every rank calls add).
         ``inputbuf`` is a list of tensors or (tensor, element_offset) pairs,
-        ``outputbuf`` a tensor or (tensor, element_offset).
+        ``outputbuf`` a tensor or (tensor, element_offset).  ``count == 0``
+        is checked and recorded nowhere, as the C plan does: ``numcomp`` is
+        hiccl_reduce_plan_numcomp.
     start()   compute.h:87-106 -- ONE batched kernel for all computes.
     wait()    compute.h:107-117.
     report()  compute.h:119-135 (local numbers; the Comm layer gathers).
@@ -172,6 +174,16 @@ class Compute:
         not honour raises HicclError."""
         cfg = L.ReduceConfig(**config)
         L.check(L.lib().hiccl_reduce_plan_set_config(self._plan, ctypes.byref(cfg)), "plan_set_config")
+
+    def set_engine(self, engine):
+        """Engine of the plan's launches (hiccl_reduce_plan_set_engine); the
+        rest of the configuration stays."""
+        L.check(L.lib().hiccl_reduce_plan_set_engine(self._plan, engine), "plan_set_engine")
+
+    def set_acc(self, acc):
+        """Accumulation mode (hiccl_reduce_plan_set_acc); the rest of the
+        configuration stays."""
+        L.check(L.lib().hiccl_reduce_plan_set_acc(self._plan, acc), "plan_set_acc")
 
     def set_peer(self, flags):
         """Peer-memory policy of the plan's launches (hiccl_reduce_plan_set_peer):
@@ -209,6 +221,8 @@ class Compute:
         tab = _ptr_table([p for _, p in ins])
         L.check(L.lib().hiccl_reduce_plan_add(self._plan, ctypes.c_void_p(op), tab, len(ins), count),
                 "plan_add")
+        if count == 0:  # validated, then dropped by the plan (a no-op): numcomp is hiccl_reduce_plan_numcomp
+            return
         self._keep.append((ot, [t for t, _ in ins]))
         self.inputbuf.append([p for _, p in ins])
         self.outputbuf.append(op)

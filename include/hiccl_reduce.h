@@ -203,7 +203,14 @@ int hiccl_reduce_auto_choice_ex(int dtype, const hiccl_reduce_config_t *cfg, siz
  *            them, compute.h:70-82).
  * Threading: launch/sync may be called from a different host thread than
  * create/add (Comm::start's pthread, comm.h:214-224); each entry binds the
- * plan's device.  Not reentrant per plan; distinct plans are independent.
+ * plan's device.  Distinct plans are independent.  One plan is not
+ * reentrant: add, the set_* calls, launch, launch_each, sync, destroy and
+ * any launch or enqueue that uploads (the first after an add or a config
+ * change) need the plan to themselves.  The one exception:
+ * hiccl_reduce_plan_enqueue of a plan that is already uploaded only reads
+ * the plan and sets an atomic flag, so several threads may enqueue the same
+ * uploaded plan at once, each onto a stream of its own (the dynamic
+ * schedule's ticket counter belongs to a device and stream).
  */
 typedef struct hiccl_reduce_plan hiccl_reduce_plan_t;
 
@@ -259,7 +266,9 @@ int hiccl_reduce_plan_add(hiccl_reduce_plan_t *plan, void *out, const void *cons
 int hiccl_reduce_plan_launch(hiccl_reduce_plan_t *plan, void *stream);
 /* launch without remembering the stream for hiccl_reduce_plan_sync: for
  * stream-ordered callers that synchronise the stream themselves, and for
- * launches from several threads onto different streams.  A later re-upload
+ * launches of an already uploaded plan from several threads, each onto a
+ * different stream (Threading, above: an enqueue that has to upload is not
+ * reentrant).  A later re-upload
  * (the first launch after an add or a config change) or destroy of a plan
  * launched this way synchronises the device before it frees the plan's
  * device table. */
