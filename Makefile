@@ -66,7 +66,8 @@ ABI_LINK = -Lhiccl_amd -lhiccl_reduce -Wl,-rpath,'$$ORIGIN/../hiccl_amd' -L/opt/
 HDRS = include/hiccl.h $(wildcard include/hiccl/*.h) include/hiccl_reduce.h hiccl_amd/csrc/compose.h
 
 CPP_BINS = build/plan_dump build/collectives_host build/collectives_host_f32 build/collectives_hip build/collectives_hip_f32 \
-           build/readme_example_host build/readme_example_hip build/abi_c build/ipc_reuse build/sync_wait_probe
+           build/readme_example_host build/readme_example_hip build/abi_c build/ipc_reuse build/sync_wait_probe \
+           build/f16_add build/f16_compute_host build/f16_compute_hip
 
 cpp: $(CPP_BINS)
 
@@ -107,6 +108,20 @@ build/ipc_reuse: tests/cpp/ipc_reuse.cpp include/hiccl_reduce.h $(LIB)
 build/sync_wait_probe: tools/sync_wait_probe.cpp include/hiccl_reduce.h $(LIB)
 	@mkdir -p build
 	$(CXX) $(CXXFLAGS) -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -o $@ $< $(ABI_LINK)
+
+# HiCCL::f16: `+=` on every bit pattern (host), and Compute<f16> on the host
+# port and on the GPU (tests/test_f16_cpu.py, tests/test_f16_gpu.py)
+build/f16_add: tests/cpp/f16_add.cpp $(HDRS)
+	@mkdir -p build
+	$(CXX) $(CXXFLAGS) -fopenmp -DHICCL_PORT_HOST -o $@ $< $(MPI_LINK)
+
+build/f16_compute_host: tests/cpp/f16_compute.cpp $(HDRS)
+	@mkdir -p build
+	$(CXX) $(CXXFLAGS) -fopenmp -DHICCL_PORT_HOST -o $@ $< $(MPI_LINK)
+
+build/f16_compute_hip: tests/cpp/f16_compute.cpp $(HDRS) $(LIB)
+	@mkdir -p build
+	$(CXX) $(CXXFLAGS) $(HIP_HOST) -o $@ $< $(HIP_LINK) $(MPI_LINK)
 
 # plain C99 client of the C ABI (the header must stay C)
 build/abi_c: tests/cpp/abi_c.c include/hiccl_reduce.h $(LIB)

@@ -24,6 +24,7 @@ HICCL_BFLOAT16 = 2
 HICCL_UINT64 = 3
 HICCL_INT32 = 4
 HICCL_BYTES = 5
+HICCL_FLOAT16 = 6
 
 HICCL_ACC_NATIVE = 0
 HICCL_ACC_WIDE = 1
@@ -45,6 +46,7 @@ DTYPE_OF_TORCH = {
     torch.float32: HICCL_FLOAT32,
     torch.float64: HICCL_FLOAT64,
     torch.bfloat16: HICCL_BFLOAT16,
+    torch.float16: HICCL_FLOAT16,
     torch.int64: HICCL_UINT64,  # two's-complement add == size_t add bit for bit
     torch.uint64: HICCL_UINT64,
     torch.int32: HICCL_INT32,
@@ -78,6 +80,7 @@ _SIGS = {
     "hiccl_reduce": (ctypes.c_int, [ctypes.c_int, _vp, _vp, ctypes.c_int, ctypes.c_size_t, _vp]),
     "hiccl_reduce_f32": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_size_t, _vp]),
     "hiccl_reduce_bf16": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_size_t, _vp]),
+    "hiccl_reduce_f16": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_size_t, _vp]),
     "hiccl_reduce_ex": (ctypes.c_int, [ctypes.c_int, _vp, _vp, ctypes.c_int, ctypes.c_size_t, _vp,
                                        ctypes.POINTER(ReduceConfig)]),
     "hiccl_reduce_auto_choice": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_size_t, ctypes.c_double,

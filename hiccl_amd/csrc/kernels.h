@@ -30,7 +30,7 @@ constexpr int kDefPol = 11;  // nt loads, nt stores
 //  tile   256 lanes x 4 packets (16 KiB per input per tile), for computes too
 //         small to give every CU several phased chunks;
 //  phase  512 lanes x P packets (P = phase_p: 16, or 8 where the accumulator
-//         of a packet takes 8 VGPRs -- bf16 WIDE -- or the adds get
+//         of a packet takes 8 VGPRs -- bf16 / f16 WIDE -- or the adds get
 //         reassociated: int32) -- 128 KiB per input per chunk (64 KiB at P = 8).
 // Both: nt loads and nt stores, one workgroup per CU, grid-stride.  Plan
 // kernels run the TILE engine at kDefBlock lanes only.
@@ -131,7 +131,7 @@ struct ProgArgs {
 // acc: HICCL_ACC_*)
 
 size_t esize(int dtype);            // bytes per element, 0 for an unknown dtype
-bool tuned_type(int dtype, int acc);  // a headline type (f32, bf16 native): the full tuning table
+bool tuned_type(int dtype, int acc);  // a headline type (f32, bf16 / f16 native): the full tuning table
 int phase_p(int dtype, int acc);    // packets per lane of the PHASE engine's default chunk
 
 // ---- kernel tables: the launcher of a shape, or NULL where no kernel has it
@@ -149,7 +149,7 @@ prog_fn pick_prog(int dtype, int unroll);
 
 void launch_sigwait_phases(const SigPhaseArgs &a, hipStream_t s);
 void launch_counter_add(uint32_t *ctr, uint32_t v, hipStream_t s);
-// false: no fill kernel for this dtype (FLOAT32 / FLOAT64 / BFLOAT16 only)
+// false: no fill kernel for this dtype (FLOAT32 / FLOAT64 / BFLOAT16 / FLOAT16 only)
 bool launch_fill(int dtype, unsigned blocks, hipStream_t s, char *out, uint64_t count, uint64_t key, uint64_t first);
 void launch_copy(unsigned blocks, hipStream_t s, void *dst, const void *src, uint64_t npkt);
 void launch_copy_bytes(hipStream_t s, char *dst, const char *src, uint64_t nbytes);

@@ -120,6 +120,11 @@ int hiccl_reduce_bf16(uint16_t *out, const uint16_t *const *in, int n, size_t co
   return hiccl_reduce_ex(HICCL_BFLOAT16, out, (const void *const *)in, n, count, stream, nullptr);
 }
 
+int hiccl_reduce_f16(uint16_t *out, const uint16_t *const *in, int n, size_t count,
+                     void *stream) {
+  return hiccl_reduce_ex(HICCL_FLOAT16, out, (const void *const *)in, n, count, stream, nullptr);
+}
+
 int hiccl_reduce_auto_choice_ex(int dtype, const hiccl_reduce_config_t *cfg, size_t count, double n, int cus,
                                 int *engine, int *unroll, int *blocks_per_cu, int *dynamic, int *store_policy) {
   const size_t esz = esize(dtype);

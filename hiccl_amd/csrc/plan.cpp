@@ -51,7 +51,7 @@ int launch_plan(PlanArgs a, int dtype, const Cfg &c, double mean_n, int dev, hip
   if (!fn)
     return fail(hipErrorInvalidValue, pol == kDefPol ? "plan: unsupported dtype / shape"
                                                      : "plan: no peer-policy kernel for this shape (PHASE default, "
-                                                       "TILE unroll 4, f32 / bf16 also 2)");
+                                                       "TILE unroll 4, f32 / bf16 / f16 also 2)");
   const LaunchShape L = launch_shape(c, mean_n, a.t_end - a.t_begin, device_cus(dev));
   a.grab = L.grab;
   a.sched = L.dynamic ? ticket_counter(dev, s) : nullptr;

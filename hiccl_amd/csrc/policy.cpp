@@ -2,6 +2,12 @@
 // engine, tile shape, workgroups per CU, schedule and store form a launch
 // takes (policy.h).  Measured numbers behind each rule: DESIGN.md sections
 // 4-5 and the profiles named here.
+//
+// f16 (HICCL_FLOAT16) takes bf16's rules unchanged, native and wide alike:
+// its bytes and packet shapes are bf16's and its ALU work is lower (one
+// v_pk_add_f16 per two elements).  None of the thresholds below has been
+// measured for f16; DESIGN.md section 5 (M17) records the one f16 / bf16
+// comparison.
 #include "policy.h"
 
 namespace hiccl_impl {
@@ -84,7 +90,7 @@ int auto_wide_unroll(uint64_t npkt, double n, int dtype, const Cfg &c, int dev) 
 int auto_engine(uint64_t npkt, double n, int dtype, const Cfg &c, int dev) {
   const int acc = c.acc;
   if (auto_wide_unroll(npkt, n, dtype, c, dev)) return HICCL_ENGINE_TILE;
-  const bool packed_ok = !(dtype == HICCL_BFLOAT16 && acc == HICCL_ACC_WIDE);
+  const bool packed_ok = !((dtype == HICCL_BFLOAT16 || dtype == HICCL_FLOAT16) && acc == HICCL_ACC_WIDE);
   // Round 5: a launch that stores write-through (store form left to size, at
   // most wt_cap written; f32, bf16) runs faster on the phased engine wherever the
   // dynamic tiles would otherwise take it -- 256 MiB per input, n = 8 / 16 /
@@ -288,9 +294,9 @@ std::string plan_shape_error(const Cfg &c, int dtype) {
   if (c.block != kDefBlock) return "plan kernels run the TILE engine at block 256 only";
   const bool wt = c.store == kPolStoreSys;
   if (wt && !wt_unroll(c.unroll))
-    return "write-through plan kernels (store_policy 4) run the TILE engine at unroll 4 (f32 / bf16: 2 or 4) only";
+    return "write-through plan kernels (store_policy 4) run the TILE engine at unroll 4 (f32 / bf16 / f16: 2 or 4) only";
   if (!pick_plan(dtype, c.acc, HICCL_ENGINE_TILE, c.unroll, plan_pol(wt ? HICCL_PEER_STORES : 0)))
-    return "plan kernels run the TILE engine at unroll 4 (f32 / bf16: 1, 2, 4, 8 or 16) only";
+    return "plan kernels run the TILE engine at unroll 4 (f32 / bf16 / f16: 1, 2, 4, 8 or 16) only";
   return "";
 }
 

@@ -61,6 +61,8 @@ typedef double f64x2 __attribute__((ext_vector_type(2)));
 typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
 typedef float f32x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
 // Buffer resources: one SGPR descriptor per input per tile (base = input +
 // tile offset, range = the tile's valid bytes).  Loads/stores then take only
@@ -230,6 +232,63 @@ struct OpBF16Wide {
     return a + __uint_as_float((uint32_t)(gld<uint16_t>(p)) << 16);
   }
   __device__ static void sstore(char *p, sacc_t a) { gst<uint16_t>(p, bf_round(a)); }
+};
+
+// fp16 (IEEE half), reference semantics: acc is half and every add is a half
+// add.  gfx950 has that add natively -- one v_pk_add_f16 adds two elements,
+// rounded to nearest even, subnormals kept (the code object's 16-bit denorm
+// mode) -- so the accumulator stays in the packet's own layout (4 VGPRs) and
+// an add costs four instructions per packet, with no widen / round pair.
+typedef _Float16 half_t;
+__device__ __forceinline__ half_t f16_ld(const char *p) { return __builtin_bit_cast(half_t, gld<uint16_t>(p)); }
+__device__ __forceinline__ float f16_widen(uint32_t w, int hi) {
+  return (float)__builtin_bit_cast(f16x2, w)[hi];
+}
+// f32 -> half is round-to-nearest-even (v_cvt_f16_f32); overflow gives Inf
+// and a NaN stays a NaN.
+__device__ __forceinline__ uint16_t f16_round(float f) { return __builtin_bit_cast(uint16_t, (half_t)f); }
+
+struct OpF16 {
+  static constexpr bool kWidens = false;
+  static constexpr int kEsz = 2;
+  typedef f16x8 acc_t;
+  __device__ static acc_t zero() { return (f16x8)((half_t)0.0f); }  // +0
+  __device__ static acc_t add(acc_t a, u32x4 p) { return a + __builtin_bit_cast(f16x8, p); }
+  __device__ static u32x4 pack(acc_t a) { return __builtin_bit_cast(u32x4, a); }
+  typedef half_t sacc_t;
+  __device__ static sacc_t szero() { return (half_t)0.0f; }
+  __device__ static sacc_t sadd(sacc_t a, const char *p) { return a + f16_ld(p); }
+  __device__ static void sstore(char *p, sacc_t a) { gst<uint16_t>(p, __builtin_bit_cast(uint16_t, a)); }
+};
+
+// fp16 inputs, f32 accumulator, one rounding at the end (HICCL_ACC_WIDE): a
+// sequential f32 sum in input order from +0, NOT reference-bitwise.
+struct OpF16Wide {
+  static constexpr bool kWidens = true;
+  static constexpr int kEsz = 2;
+  typedef f32x8 acc_t;
+  __device__ static acc_t zero() { return (f32x8)(0.0f); }
+  __device__ static acc_t add(acc_t a, u32x4 p) {
+#pragma unroll
+    for (int w = 0; w < 4; w++) {
+      a[2 * w] += f16_widen(p[w], 0);
+      a[2 * w + 1] += f16_widen(p[w], 1);
+    }
+    return a;
+  }
+  __device__ static u32x4 pack(acc_t a) {
+    u32x4 r;
+#pragma unroll
+    for (int w = 0; w < 4; w++) {
+      f16x2 v = {(half_t)a[2 * w], (half_t)a[2 * w + 1]};
+      r[w] = __builtin_bit_cast(uint32_t, v);
+    }
+    return r;
+  }
+  typedef float sacc_t;
+  __device__ static sacc_t szero() { return 0.0f; }
+  __device__ static sacc_t sadd(sacc_t a, const char *p) { return a + (float)f16_ld(p); }
+  __device__ static void sstore(char *p, sacc_t a) { gst<uint16_t>(p, f16_round(a)); }
 };
 
 // Exact byte copy (HICCL_BYTES): one input, out = in[0] bit for bit.  The
@@ -681,6 +740,7 @@ __global__ __launch_bounds__(256) void k_fill(char *out, uint64_t count, uint64_
     if constexpr (DT == HICCL_FLOAT32) ((float *)out)[i] = v;
     if constexpr (DT == HICCL_FLOAT64) ((double *)out)[i] = (double)v;
     if constexpr (DT == HICCL_BFLOAT16) ((uint16_t *)out)[i] = bf_round(v);
+    if constexpr (DT == HICCL_FLOAT16) ((uint16_t *)out)[i] = f16_round(v);
   }
 }
 
@@ -954,7 +1014,7 @@ __global__ __launch_bounds__(kProgBlock) void k_program(ProgArgs a) {
 // ------------------------------------------------------- kernel tables ----
 
 // The one list of element types: (dtype, acc) -> (element op, tuned).  The
-// headline types (f32, bf16 with the native accumulator) are TUNED: they get
+// headline types (f32, bf16 and f16 with the native accumulator) are TUNED: they get
 // the full tuning table, the others every engine's default shape.  Every
 // per-dtype lookup below goes through it.
 template <int DT, class O, bool TUNED>
@@ -971,6 +1031,9 @@ R with_elem(int dtype, int acc, R unknown, F f) {
     case HICCL_BFLOAT16:
       return acc == HICCL_ACC_WIDE ? f(Elem<HICCL_BFLOAT16, OpBF16Wide, false>())
                                    : f(Elem<HICCL_BFLOAT16, OpBF16, true>());
+    case HICCL_FLOAT16:
+      return acc == HICCL_ACC_WIDE ? f(Elem<HICCL_FLOAT16, OpF16Wide, false>())
+                                   : f(Elem<HICCL_FLOAT16, OpF16, true>());
     case HICCL_FLOAT64: return f(Elem<HICCL_FLOAT64, OpF64, false>());
     case HICCL_UINT64: return f(Elem<HICCL_UINT64, OpU64, false>());
     case HICCL_INT32: return f(Elem<HICCL_INT32, OpI32, false>());
@@ -981,7 +1044,7 @@ R with_elem(int dtype, int acc, R unknown, F f) {
 
 // P of the phased engine: 16 packets per lane (acc + two in-flight loads =
 // 3 x 64 VGPRs at 512 lanes) unless the accumulator is wider than a packet
-// (bf16: f32x8) or the compiler reassociates the adds and holds more
+// (bf16 / f16 wide: f32x8) or the compiler reassociates the adds and holds more
 // registers (int32: exact, so it may) -- then 8.
 template <class Op>
 constexpr int phase_p_of() {
@@ -1073,7 +1136,7 @@ single_fn pick_single_op(int engine, int block, int unroll, int pol) {
 // Plan kernels (and one-shot calls with > 64 inputs, which run as a
 // one-compute plan) come in the PHASE engine's default shape and the TILE
 // engine at 256 lanes x U packets, U = 4 for every type and also 1 or 2 for
-// the headline types (f32, bf16 native).  Cache policy: nt loads and stores.
+// the headline types (f32, bf16 / f16 native).  Cache policy: nt loads and stores.
 
 template <class Op, int ENG, int U, int POL = kDefPol>
 void launch_plan_t(const PlanArgs &a, dim3 grid, hipStream_t s) {
@@ -1158,7 +1221,7 @@ prog_fn pick_prog(int dtype, int unroll) {
   // programs accumulate natively only (hiccl_program_add_plan)
   return with_elem(dtype, HICCL_ACC_NATIVE, (prog_fn) nullptr, [&](auto e) -> prog_fn {
     typedef decltype(e) E;
-    if constexpr (std::is_same<typename E::Op, OpBF16Wide>::value) return nullptr;
+    if constexpr (sizeof(typename E::Op::acc_t) > kPacket) return nullptr;  // the f32-accumulating ops
     else if (unroll != 2) return launch_prog_t<typename E::Op, 4>;
     else if constexpr (E::tuned) return launch_prog_t<typename E::Op, 2>;
     else return nullptr;
@@ -1176,8 +1239,9 @@ void launch_counter_add(uint32_t *ctr, uint32_t v, hipStream_t s) {
 bool launch_fill(int dtype, unsigned blocks, hipStream_t s, char *out, uint64_t count, uint64_t key, uint64_t first) {
   return with_elem(dtype, HICCL_ACC_NATIVE, false, [&](auto e) {
     typedef decltype(e) E;
-    // the floating types: f32, f64, bf16
-    if constexpr (std::is_floating_point<typename E::Op::sacc_t>::value) {
+    // the floating types: f32, f64, bf16, f16
+    if constexpr (std::is_floating_point<typename E::Op::sacc_t>::value ||
+                  std::is_same<typename E::Op::sacc_t, half_t>::value) {
       hipLaunchKernelGGL(k_fill<E::dtype>, dim3(blocks), dim3(256), 0, s, out, count, key, first);
       return true;
     } else {

@@ -2,7 +2,7 @@
 // facts, synthetic inputs, stream copies, bucket allocations.
 #include "runtime.h"
 
-#define HICCL_VERSION_INT 100  // 0.1.0
+#define HICCL_VERSION_INT 200  // 0.2.0 (0.2: HICCL_FLOAT16)
 
 using namespace hiccl_impl;
 
@@ -30,7 +30,7 @@ int hiccl_fill_uniform(int dtype, void *out, size_t count, uint64_t seed, uint32
   const uint64_t cap = (uint64_t)device_cus(current_device()) * 16;
   if (blocks > cap) blocks = cap;
   if (!launch_fill(dtype, (unsigned)blocks, (hipStream_t)stream, (char *)out, (uint64_t)count, key, (uint64_t)first))
-    return fail(hipErrorInvalidValue, "fill_uniform: dtype must be FLOAT32/FLOAT64/BFLOAT16");
+    return fail(hipErrorInvalidValue, "fill_uniform: dtype must be FLOAT32/FLOAT64/BFLOAT16/FLOAT16");
   return check_hip(hipGetLastError(), "fill_uniform: launch");
 }
 

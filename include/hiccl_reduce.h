@@ -31,8 +31,8 @@ extern "C" {
 
 /* Element types.  The reference is a template over T (compute.h:26); its
  * drivers instantiate T = size_t (collectives/main.cpp:24, main.cpp:4) and
- * T = float (main.cu:10).  bf16 follows `T acc; acc += x` semantics
- * (round to bf16 after every add) unless HICCL_ACC_WIDE is requested. */
+ * T = float (main.cu:10).  bf16 and f16 (IEEE half) follow `T acc; acc += x`
+ * semantics (round to T after every add) unless HICCL_ACC_WIDE is requested. */
 typedef enum {
   HICCL_FLOAT32 = 0,
   HICCL_FLOAT64 = 1,
@@ -40,13 +40,15 @@ typedef enum {
   HICCL_UINT64 = 3, /* size_t */
   HICCL_INT32 = 4,
   HICCL_BYTES = 5,  /* exact copy, exactly one input: out = in[0] (transport data movement) */
-  HICCL_NUM_DTYPES = 6
+  HICCL_FLOAT16 = 6, /* IEEE binary16 */
+  HICCL_NUM_DTYPES = 7
 } hiccl_dtype_t;
 
-/* Accumulation mode (only meaningful for HICCL_BFLOAT16). */
+/* Accumulation mode (only meaningful for the 2-byte float types,
+ * HICCL_BFLOAT16 and HICCL_FLOAT16). */
 typedef enum {
   HICCL_ACC_NATIVE = 0, /* accumulate in T: reference semantics (default) */
-  HICCL_ACC_WIDE = 1    /* accumulate bf16 in f32, round once: NOT reference-bitwise */
+  HICCL_ACC_WIDE = 1    /* accumulate bf16 / f16 in f32, round once: NOT reference-bitwise */
 } hiccl_acc_t;
 
 /* Kernel engine (both compute the same bits; they differ in access order).
@@ -55,10 +57,10 @@ typedef enum {
  *          ... (next input's loads in flight while the current one is
  *          added), then writes the chunk.
  *   AUTO   TILE (on the dynamic schedule, below) with >= 5 inputs once
- *          every workgroup gets >= 64 tickets (bf16: packed accumulator
- *          only); TILE with 32 KiB-per-input tiles (unroll 8) on the
+ *          every workgroup gets >= 64 tickets (bf16 / f16: native
+ *          accumulator only); TILE with 32 KiB-per-input tiles (unroll 8) on the
  *          dynamic schedule with 2-4 inputs once every workgroup gets
- *          >= 128 of them (1 GiB per input, f32 / bf16); otherwise PHASE
+ *          >= 128 of them (1 GiB per input, f32 / bf16 / f16); otherwise PHASE
  *          when its chunks fill the CUs: >= 1 chunk per CU with >= 5
  *          inputs (with >= 16 inputs and 128 KiB chunks 0.7 suffice), >= 4
  *          with 3-4, > 16 with 2, in rounds of chunks that keep >= 70 % (64
@@ -119,6 +121,8 @@ int hiccl_reduce(int dtype, void *out, const void *const *in, int n, size_t coun
 int hiccl_reduce_f32(float *out, const float *const *in, int n, size_t count, void *stream);
 int hiccl_reduce_bf16(uint16_t *out, const uint16_t *const *in, int n, size_t count,
                       void *stream);
+int hiccl_reduce_f16(uint16_t *out, const uint16_t *const *in, int n, size_t count,
+                     void *stream);
 
 /* Tuning knobs of the single-compute kernel.  Zero fields mean "default".
  * With engine AUTO, a non-zero block or unroll selects the TILE engine.
@@ -129,7 +133,8 @@ int hiccl_reduce_bf16(uint16_t *out, const uint16_t *const *in, int n, size_t co
 typedef struct {
   int block;         /* threads per workgroup: TILE 256 or 512; PHASE 256, 512 or 1024 */
   int unroll;        /* 16-byte packets per input per lane per tile: TILE 1, 2 or 4 (block
-                        256, f32 / bf16: also 8 or 16 -- wide tiles for few inputs);
+                        256, f32 / bf16 / f16: also 8 or 16 -- wide tiles for few
+                        inputs);
                         PHASE 4, 8 or 16 (chunk = block * unroll * 16 B) */
   int blocks_per_cu; /* persistent grid = CUs x this (capped by tiles) */
   int nontemporal;   /* loads: 1 plain cache policy, 2 nt */
@@ -221,8 +226,8 @@ int hiccl_reduce_plan_set_acc(hiccl_reduce_plan_t *plan, int acc);
 int hiccl_reduce_plan_set_engine(hiccl_reduce_plan_t *plan, int engine);
 /* Kernel configuration of the plan's launches (NULL = all defaults; replaces
  * earlier set_engine / set_acc choices).  Honoured: engine, schedule, grab,
- * blocks_per_cu, grid, acc, and the TILE shape block 256 x unroll 4 (f32 and
- * bf16 also unroll 1, 2, 8 or 16); PHASE runs its default shape; loads are
+ * blocks_per_cu, grid, acc, and the TILE shape block 256 x unroll 4 (f32,
+ * bf16 and f16 also unroll 1, 2, 8 or 16); PHASE runs its default shape; loads are
  * nt; stores are nt (store_policy 2), system-scope write-through (4), or
  * (0, the default) write-through when a launch writes at most 256 MiB of
  * sums or 32 MiB of byte copies and nt above -- pipeline steps and mid-size
@@ -245,7 +250,7 @@ int hiccl_reduce_plan_set_config(hiccl_reduce_plan_t *plan, const hiccl_reduce_c
  *   HICCL_PEER_LOADS   every load is system-scope coherent (no L2 line of a
  *                      peer's buffer cached by an earlier launch is served).
  * Same results; runs the PHASE engine's default shape and TILE at unroll 4
- * (f32 / bf16 also 2): an automatic wide-tile choice becomes unroll 4, an
+ * (f32 / bf16 / f16 also 2): an automatic wide-tile choice becomes unroll 4, an
  * explicit unroll the peer kernels lack fails at launch.  Kept by
  * hiccl_program_add_plan for the plan's computes. */
 typedef enum {
@@ -442,7 +447,8 @@ int hiccl_step_program_default(void);
  *
  * fill_uniform: element i of buffer k = uniform [-1,1) value of hash
  * (seed, k, first + i), identical to oracle/reduce_oracle.c's generator
- * (dtypes FLOAT32, BFLOAT16, FLOAT64).
+ * (dtypes FLOAT32, BFLOAT16, FLOAT64; FLOAT16: the same f32 value rounded to
+ * nearest-even half).
  * stream_copy: plain 16-byte-per-lane device copy, the achievable-bandwidth
  * ceiling reference for the roofline.
  */
