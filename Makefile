@@ -14,8 +14,10 @@ all: $(LIB) $(PROBE) cpp oracle
 $(PROBE): tools/hbm_probe.hip
 	$(HIPCC) $(HIPFLAGS) -o $@ $<
 
-# The library: one kernel translation unit (reduce.hip, minutes to compile)
-# and the host files (seconds each), as objects under build/obj, linked once.
+# The library: two kernel translation units over one header of templates
+# (engine.h) -- reduce.hip, the SUM kernels, and reduce_ops.hip, the MAX / MIN
+# kernels, minutes each and compiled side by side -- and the host files
+# (seconds each), as objects under build/obj, linked once.
 # Both are compiled by hipcc's clang at -O3 without fast-math (the AUTO rules
 # compare doubles) and without per-thread default streams; the host files as
 # plain C++, so they carry no device code.
@@ -23,14 +25,15 @@ CSRC = hiccl_amd/csrc
 OBJDIR = build/obj
 OBJFLAGS = -O3 -fPIC -std=c++17 -Wall -MMD -MP
 LIB_HOST = runtime policy oneshot plan host_pipe signal program util
-LIB_OBJS = $(OBJDIR)/reduce.o $(LIB_HOST:%=$(OBJDIR)/%.o)
+LIB_KERNELS = reduce reduce_ops
+LIB_OBJS = $(LIB_KERNELS:%=$(OBJDIR)/%.o) $(LIB_HOST:%=$(OBJDIR)/%.o)
 
 # The atomic optimizer rewrites the one-lane unit-ticket grab into a
 # wave-reduction whose result is read back at once (s_waitcnt vmcnt(0) at the
 # top of every unit); without it the wait lands after the unit's last add.
 LIBFLAGS = -mllvm -amdgpu-atomic-optimizer-strategy=None
 
-$(OBJDIR)/reduce.o: $(CSRC)/reduce.hip
+$(OBJDIR)/%.o: $(CSRC)/%.hip
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) --offload-arch=$(ARCH) $(OBJFLAGS) $(LIBFLAGS) -c -o $@ $<
 
@@ -67,7 +70,8 @@ HDRS = include/hiccl.h $(wildcard include/hiccl/*.h) include/hiccl_reduce.h hicc
 
 CPP_BINS = build/plan_dump build/collectives_host build/collectives_host_f32 build/collectives_hip build/collectives_hip_f32 \
            build/readme_example_host build/readme_example_hip build/abi_c build/ipc_reuse build/sync_wait_probe \
-           build/f16_add build/f16_compute_host build/f16_compute_hip
+           build/f16_add build/f16_compute_host build/f16_compute_hip \
+           build/ops_add build/ops_compute_host build/ops_compute_hip build/ops_comm_host build/ops_comm_hip
 
 cpp: $(CPP_BINS)
 
@@ -120,6 +124,30 @@ build/f16_compute_host: tests/cpp/f16_compute.cpp $(HDRS)
 	$(CXX) $(CXXFLAGS) -fopenmp -DHICCL_PORT_HOST -o $@ $< $(MPI_LINK)
 
 build/f16_compute_hip: tests/cpp/f16_compute.cpp $(HDRS) $(LIB)
+	@mkdir -p build
+	$(CXX) $(CXXFLAGS) $(HIP_HOST) -o $@ $< $(HIP_LINK) $(MPI_LINK)
+
+# HiCCL::maxof / minof (include/hiccl/ops.h): `+=` against the NumPy
+# restatement (host), and Compute<maxof<float>> / Compute<minof<bf16>> on the
+# host port and on the GPU (tests/test_ops_cpu.py, tests/test_ops_gpu.py)
+build/ops_add: tests/cpp/ops_add.cpp $(HDRS)
+	@mkdir -p build
+	$(CXX) $(CXXFLAGS) -fopenmp -DHICCL_PORT_HOST -o $@ $< $(MPI_LINK)
+
+build/ops_compute_host: tests/cpp/ops_compute.cpp $(HDRS)
+	@mkdir -p build
+	$(CXX) $(CXXFLAGS) -fopenmp -DHICCL_PORT_HOST -o $@ $< $(MPI_LINK)
+
+build/ops_compute_hip: tests/cpp/ops_compute.cpp $(HDRS) $(LIB)
+	@mkdir -p build
+	$(CXX) $(CXXFLAGS) $(HIP_HOST) -o $@ $< $(HIP_LINK) $(MPI_LINK)
+
+# Comm<maxof<float>>: a reduce to root under MPI (tests/test_ops_cpu.py host, tests/test_ops_gpu.py GPU)
+build/ops_comm_host: tests/cpp/ops_comm.cpp $(HDRS)
+	@mkdir -p build
+	$(CXX) $(CXXFLAGS) -fopenmp -DHICCL_PORT_HOST -o $@ $< $(MPI_LINK)
+
+build/ops_comm_hip: tests/cpp/ops_comm.cpp $(HDRS) $(LIB)
 	@mkdir -p build
 	$(CXX) $(CXXFLAGS) $(HIP_HOST) -o $@ $< $(HIP_LINK) $(MPI_LINK)
 

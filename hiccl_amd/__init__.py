@@ -6,9 +6,10 @@ behind the C ABI of include/hiccl_reduce.h; the C++ drop-in surface
 package is the binding used by the tests and bench.py.
 """
 from ._lib import (HICCL_ACC_NATIVE, HICCL_ACC_WIDE, HICCL_BFLOAT16, HICCL_ENGINE_AUTO,  # noqa: F401
-                   HICCL_ENGINE_PHASE, HICCL_ENGINE_TILE, HICCL_FLOAT16, HICCL_FLOAT32, HICCL_FLOAT64, HICCL_INT32, HICCL_UINT64, HicclError, LIB_PATH, header_functions,
+                   HICCL_ENGINE_PHASE, HICCL_ENGINE_TILE, HICCL_FLOAT16, HICCL_FLOAT32, HICCL_FLOAT64, HICCL_INT32, HICCL_UINT64,
+                   HICCL_OP_MAX, HICCL_OP_MIN, HICCL_OP_SUM, HicclError, LIB_PATH, header_functions,
                    lib)
 from .compute import (Compute, HostPipe, Program, auto_choice, bucket, fill_uniform, reduce, reduce_ptrs,  # noqa: F401
                       stream_copy)
 
-__version__ = "0.2.0"
+__version__ = "0.3.0"

@@ -29,6 +29,10 @@ HICCL_FLOAT16 = 6
 HICCL_ACC_NATIVE = 0
 HICCL_ACC_WIDE = 1
 
+HICCL_OP_SUM = 0
+HICCL_OP_MAX = 1
+HICCL_OP_MIN = 2
+
 HICCL_ENGINE_AUTO = 0
 HICCL_ENGINE_TILE = 1
 HICCL_ENGINE_PHASE = 2
@@ -83,6 +87,14 @@ _SIGS = {
     "hiccl_reduce_f16": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_size_t, _vp]),
     "hiccl_reduce_ex": (ctypes.c_int, [ctypes.c_int, _vp, _vp, ctypes.c_int, ctypes.c_size_t, _vp,
                                        ctypes.POINTER(ReduceConfig)]),
+    "hiccl_reduce_op": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _vp, _vp, ctypes.c_int, ctypes.c_size_t, _vp,
+                                       ctypes.POINTER(ReduceConfig)]),
+    "hiccl_reduce_auto_choice_op": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ReduceConfig),
+                                                   ctypes.c_size_t, ctypes.c_double, ctypes.c_int, _vp, _vp, _vp, _vp,
+                                                   _vp]),
+    "hiccl_reduce_plan_set_op": (ctypes.c_int, [_vp, ctypes.c_int]),
+    "hiccl_reduce_plan_op": (ctypes.c_int, [_vp]),
+    "hiccl_host_pipe_set_op": (ctypes.c_int, [_vp, ctypes.c_int]),
     "hiccl_reduce_auto_choice": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_size_t, ctypes.c_double,
                                                 ctypes.c_int, _vp, _vp, _vp, _vp]),
     "hiccl_reduce_auto_choice_ex": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ReduceConfig), ctypes.c_size_t,

@@ -35,6 +35,13 @@ def _dtype_code(t):
         raise TypeError(f"hiccl: unsupported dtype {t.dtype}") from None
 
 
+def _check_op(op, dtype):
+    """torch.int64 stands for size_t under SUM only (two's-complement adds
+    are the same bits); MAX and MIN on HICCL_UINT64 compare unsigned."""
+    if op != L.HICCL_OP_SUM and dtype == torch.int64:
+        raise TypeError("hiccl: MAX / MIN on HICCL_UINT64 compare unsigned: pass torch.uint64, not torch.int64")
+
+
 def _check_tensor(t, what):
     if not isinstance(t, torch.Tensor):
         raise TypeError(f"hiccl: {what} must be a torch.Tensor")
@@ -44,8 +51,12 @@ def _check_tensor(t, what):
         raise ValueError(f"hiccl: {what} must be contiguous")
 
 
-def reduce(out, inputs, count=None, stream=None, config=None):
+def reduce(out, inputs, count=None, stream=None, config=None, op=L.HICCL_OP_SUM):
     """out[:count] = ((0 + inputs[0]) + inputs[1]) + ... in the list order.
+
+    ``op``: HICCL_OP_SUM (default), HICCL_OP_MAX or HICCL_OP_MIN -- the same
+    fold from the operator's identity (IEEE 754-2019 maximum / minimum on the
+    floating types: a NaN input gives NaN, -0 < +0; hiccl_reduce_op).
 
     Mirrors one compute of compute.h: inputs are summed in list order with
     the accumulator starting at 0 in the element type.  ``out`` may be one
@@ -70,10 +81,14 @@ def reduce(out, inputs, count=None, stream=None, config=None):
         ptrs.append(x.data_ptr())
     if out.numel() < count:
         raise ValueError(f"hiccl: out has {out.numel()} < count={count} elements")
+    _check_op(op, out.dtype)
     tab = _ptr_table(ptrs)
     with torch.cuda.device(out.device):  # the library launches on the current device
         s = _stream_handle(stream, out.device)
-        if config is None:
+        if op != L.HICCL_OP_SUM:
+            cfg = ctypes.byref(L.ReduceConfig(**config)) if config is not None else None
+            rc = L.lib().hiccl_reduce_op(dt, op, ctypes.c_void_p(out.data_ptr()), tab, len(ptrs), count, s, cfg)
+        elif config is None:
             rc = L.lib().hiccl_reduce(dt, ctypes.c_void_p(out.data_ptr()), tab, len(ptrs), count, s)
         else:
             cfg = L.ReduceConfig(**config)
@@ -83,11 +98,14 @@ def reduce(out, inputs, count=None, stream=None, config=None):
     return out
 
 
-def reduce_ptrs(dtype_code, out_ptr, in_ptrs, count, stream=None, config=None):
+def reduce_ptrs(dtype_code, out_ptr, in_ptrs, count, stream=None, config=None, op=L.HICCL_OP_SUM):
     """Raw-pointer form (pointers already offset), used by the Comm layer."""
     tab = _ptr_table(list(in_ptrs))
     s = _stream_handle(stream)
-    if config is None:
+    if op != L.HICCL_OP_SUM:
+        cfg = ctypes.byref(L.ReduceConfig(**config)) if config is not None else None
+        rc = L.lib().hiccl_reduce_op(dtype_code, op, ctypes.c_void_p(out_ptr), tab, len(in_ptrs), count, s, cfg)
+    elif config is None:
         rc = L.lib().hiccl_reduce(dtype_code, ctypes.c_void_p(out_ptr), tab, len(in_ptrs), count, s)
     else:
         cfg = L.ReduceConfig(**config)
@@ -115,18 +133,22 @@ def bucket(n, count, dtype=torch.float32, device=None):
     return views[:n], views[n]
 
 
-def auto_choice(dtype, count, n, config=None, cus=256):
+def auto_choice(dtype, count, n, config=None, cus=256, op=L.HICCL_OP_SUM):
     """What a one-shot call (and a one-compute plan at TILE unroll 2 / 4 or
     AUTO) resolves to on a GPU of ``cus`` CUs, without a device:
-    ``hiccl_reduce_auto_choice_ex``.  ``dtype``: a torch dtype or an
+    ``hiccl_reduce_auto_choice_ex`` (``op`` other than SUM:
+    ``hiccl_reduce_auto_choice_op``).  ``dtype``: a torch dtype or an
     HICCL_* code; ``n`` may be a plan's packet-weighted mean.  Returns a dict
     with engine, unroll, blocks_per_cu, dynamic and store_policy (2 nt, 4
     write-through); raises HicclError for a config no kernel has."""
     dt = L.DTYPE_OF_TORCH[dtype] if isinstance(dtype, torch.dtype) else int(dtype)
     cfg = ctypes.byref(L.ReduceConfig(**config)) if config else None
     out = [ctypes.c_int() for _ in range(5)]
-    rc = L.lib().hiccl_reduce_auto_choice_ex(dt, cfg, count, float(n), cus, *[ctypes.byref(v) for v in out])
-    L.check(rc, "hiccl_reduce_auto_choice_ex")
+    if op != L.HICCL_OP_SUM:
+        rc = L.lib().hiccl_reduce_auto_choice_op(dt, op, cfg, count, float(n), cus, *[ctypes.byref(v) for v in out])
+    else:
+        rc = L.lib().hiccl_reduce_auto_choice_ex(dt, cfg, count, float(n), cus, *[ctypes.byref(v) for v in out])
+    L.check(rc, "hiccl_reduce_auto_choice")
     return dict(zip(("engine", "unroll", "blocks_per_cu", "dynamic", "store_policy"), (v.value for v in out)))
 
 
@@ -146,7 +168,7 @@ class Compute:
     """
 
     def __init__(self, dtype=torch.float32, device=None, myid=0, acc=L.HICCL_ACC_NATIVE,
-                 engine=L.HICCL_ENGINE_AUTO, config=None):
+                 engine=L.HICCL_ENGINE_AUTO, config=None, op=L.HICCL_OP_SUM):
         self.dtype = dtype
         self.code = L.DTYPE_OF_TORCH[dtype]
         if device is None:
@@ -167,6 +189,17 @@ class Compute:
             L.check(L.lib().hiccl_reduce_plan_set_engine(self._plan, engine), "plan_set_engine")
         if config is not None:
             self.set_config(config)
+        if op != L.HICCL_OP_SUM:
+            self.set_op(op)
+
+    def set_op(self, op):
+        """Operator of the plan's launches (hiccl_reduce_plan_set_op:
+        HICCL_OP_SUM / _MAX / _MIN), at any time; the next launch re-uploads."""
+        _check_op(op, self.dtype)
+        L.check(L.lib().hiccl_reduce_plan_set_op(self._plan, op), "plan_set_op")
+
+    def op(self):
+        return L.lib().hiccl_reduce_plan_op(self._plan)
 
     def set_config(self, config):
         """Kernel configuration of the plan (dict of hiccl_reduce_config_t
@@ -367,9 +400,10 @@ class HostPipe:
     ``reduce(out, inputs)`` sums host tensors in list order on the GPU,
     staging ``chunk_bytes`` per input through device memory with H2D /
     kernel / D2H pipelined over ``depth`` streams.  Blocking; same bits as
-    :func:`reduce`.  Pin the tensors (``pin_memory()``) for the overlap."""
+    :func:`reduce`.  Pin the tensors (``pin_memory()``) for the overlap.
+    ``op``: the operator (hiccl_host_pipe_set_op), default SUM."""
 
-    def __init__(self, dtype=torch.float32, device=None, chunk_bytes=0, depth=0):
+    def __init__(self, dtype=torch.float32, device=None, chunk_bytes=0, depth=0, op=L.HICCL_OP_SUM):
         self.dtype = dtype
         self.code = L.DTYPE_OF_TORCH[dtype]
         if device is None:
@@ -378,6 +412,9 @@ class HostPipe:
         L.check(L.lib().hiccl_host_pipe_create(ctypes.byref(h), self.code, device, chunk_bytes, depth),
                 "host_pipe_create")
         self._pipe = h
+        if op != L.HICCL_OP_SUM:
+            _check_op(op, dtype)
+            L.check(L.lib().hiccl_host_pipe_set_op(self._pipe, op), "host_pipe_set_op")
 
     def reduce(self, out, inputs, count=None):
         for k, t in enumerate([out] + list(inputs)):

@@ -2,13 +2,14 @@
 // reduced on the GPU through a pipeline of staged chunks.
 #include <vector>
 
-#include "runtime.h"
+#include "policy.h"
 
 using namespace hiccl_impl;
 
 struct hiccl_host_pipe {
   int dtype = 0;
   int device = 0;
+  int op = HICCL_OP_SUM;  // hiccl_host_pipe_set_op
   size_t esz = 0;
   size_t chunk = 0;  // elements per input per chunk
   int depth = 0;
@@ -94,7 +95,7 @@ int hiccl_host_pipe_reduce(hiccl_host_pipe_t *p, void *out, const void *const *i
                       "host_pipe_reduce: H2D");
     }
     // in place into staged input 0 (exact aliasing is element-wise safe)
-    if (!err) err = hiccl_reduce_ex(p->dtype, stage, dev_in.data(), n, len, s, nullptr);
+    if (!err) err = hiccl_reduce_op(p->dtype, p->op, stage, dev_in.data(), n, len, s, nullptr);
     if (!err)
       err = check_hip(hipMemcpyAsync((char *)out + lo * p->esz, stage, len * p->esz, hipMemcpyDeviceToHost, s),
                       "host_pipe_reduce: D2H");
@@ -104,6 +105,13 @@ int hiccl_host_pipe_reduce(hiccl_host_pipe_t *p, void *out, const void *const *i
     if (!err) err = e;
   }
   return err;
+}
+
+int hiccl_host_pipe_set_op(hiccl_host_pipe_t *p, int op) {
+  if (!p) return fail(hipErrorInvalidValue, "host_pipe_set_op: pipe is NULL");
+  if (int e = check_op(p->dtype, HICCL_ACC_NATIVE, op, "host_pipe_set_op")) return e;
+  p->op = op;
+  return 0;
 }
 
 void hiccl_host_pipe_destroy(hiccl_host_pipe_t *p) {

@@ -127,12 +127,13 @@ struct ProgArgs {
   uint32_t epoch[kProgMaxPhases];  // per launch: phase p stores / awaits epoch[p] (+ *epoch_dev)
 };
 
-// ---- what reduce.hip's one list of element types answers (dtype: HICCL_*,
-// acc: HICCL_ACC_*)
+// ---- what the one list of element types (engine.h) answers (dtype: HICCL_*,
+// acc: HICCL_ACC_*, op: HICCL_OP_*)
 
 size_t esize(int dtype);            // bytes per element, 0 for an unknown dtype
-bool tuned_type(int dtype, int acc);  // a headline type (f32, bf16 / f16 native): the full tuning table
-int phase_p(int dtype, int acc);    // packets per lane of the PHASE engine's default chunk
+// a headline type (f32, bf16 / f16 native) under SUM: the full tuning table
+bool tuned_type(int dtype, int acc, int op);
+int phase_p(int dtype, int acc);    // packets per lane of the PHASE engine's default chunk (any op)
 
 // ---- kernel tables: the launcher of a shape, or NULL where no kernel has it
 // (engine: HICCL_ENGINE_TILE / _PHASE; pol: 10*store + load)
@@ -141,9 +142,13 @@ typedef void (*single_fn)(SingleArgs, dim3, hipStream_t);
 typedef void (*plan_fn)(const PlanArgs &, dim3, hipStream_t);
 typedef void (*prog_fn)(const ProgArgs &, dim3, hipStream_t);
 
-single_fn pick_single(int dtype, int acc, int engine, int block, int unroll, int pol);
-plan_fn pick_plan(int dtype, int acc, int engine, int unroll, int pol = kDefPol);
-prog_fn pick_prog(int dtype, int unroll);
+single_fn pick_single(int dtype, int acc, int op, int engine, int block, int unroll, int pol);
+plan_fn pick_plan(int dtype, int acc, int op, int engine, int unroll, int pol = kDefPol);
+prog_fn pick_prog(int dtype, int op, int unroll);
+// the MAX / MIN half of the tables (reduce_ops.hip), reached through the three above
+single_fn pick_single_maxmin(int dtype, int acc, int op, int engine, int block, int unroll, int pol);
+plan_fn pick_plan_maxmin(int dtype, int acc, int op, int engine, int unroll, int pol);
+prog_fn pick_prog_maxmin(int dtype, int op, int unroll);
 
 // ---- the plain kernels
 

@@ -52,10 +52,11 @@ int reduce_via_table(int dtype, const Cfg &c, void *out, const void *const *in, 
 
 extern "C" {
 
-int hiccl_reduce_ex(int dtype, void *out, const void *const *in, int n, size_t count,
+int hiccl_reduce_op(int dtype, int op, void *out, const void *const *in, int n, size_t count,
                     void *stream, const hiccl_reduce_config_t *cfg) {
   const size_t esz = esize(dtype);
   if (!esz) return fail(hipErrorInvalidValue, "hiccl_reduce: unknown dtype " + std::to_string(dtype));
+  if (int e = check_op(dtype, cfg ? cfg->acc : HICCL_ACC_NATIVE, op, "hiccl_reduce")) return e;
   if (count == 0) return 0;
   if (dtype == HICCL_BYTES && n != 1) return fail(hipErrorInvalidValue, "hiccl_reduce: HICCL_BYTES copies need n == 1");
   if (int e = check_buffers(out, in, n, count, esz)) return e;
@@ -64,7 +65,7 @@ int hiccl_reduce_ex(int dtype, void *out, const void *const *in, int n, size_t c
   const int dev = current_device();
   Split sp = split_on(out, count, esz);
   // engine, shape and store form (write-through by size, as a plan's)
-  Cfg c = oneshot_cfg(dtype, cfg, sp.npkt, (uint64_t)count * esz, n, dev);
+  Cfg c = oneshot_cfg(dtype, op, cfg, sp.npkt, (uint64_t)count * esz, n, dev);
   if (n > kMaxArgInputs) {
     const std::string why = plan_shape_error(c, dtype);
     if (!why.empty()) return fail(hipErrorInvalidValue, "hiccl_reduce_ex: n > 64 inputs run on the plan kernel: " + why);
@@ -107,6 +108,11 @@ int hiccl_reduce_ex(int dtype, void *out, const void *const *in, int n, size_t c
   return check_hip(hipGetLastError(), "hiccl_reduce: launch");
 }
 
+int hiccl_reduce_ex(int dtype, void *out, const void *const *in, int n, size_t count,
+                    void *stream, const hiccl_reduce_config_t *cfg) {
+  return hiccl_reduce_op(dtype, HICCL_OP_SUM, out, in, n, count, stream, cfg);
+}
+
 int hiccl_reduce(int dtype, void *out, const void *const *in, int n, size_t count, void *stream) {
   return hiccl_reduce_ex(dtype, out, in, n, count, stream, nullptr);
 }
@@ -125,15 +131,16 @@ int hiccl_reduce_f16(uint16_t *out, const uint16_t *const *in, int n, size_t cou
   return hiccl_reduce_ex(HICCL_FLOAT16, out, (const void *const *)in, n, count, stream, nullptr);
 }
 
-int hiccl_reduce_auto_choice_ex(int dtype, const hiccl_reduce_config_t *cfg, size_t count, double n, int cus,
+int hiccl_reduce_auto_choice_op(int dtype, int op, const hiccl_reduce_config_t *cfg, size_t count, double n, int cus,
                                 int *engine, int *unroll, int *blocks_per_cu, int *dynamic, int *store_policy) {
   const size_t esz = esize(dtype);
   if (!esz) return fail(hipErrorInvalidValue, "auto_choice: unknown dtype");
+  if (int e = check_op(dtype, cfg ? cfg->acc : HICCL_ACC_NATIVE, op, "auto_choice")) return e;
   if (cus <= 0 || n < 0) return fail(hipErrorInvalidValue, "auto_choice: cus must be > 0 and n >= 0");
   if (int e = check_cfg(cfg, "auto_choice")) return e;
   CusOverride scoped(cus);  // no device query: the choice for `cus` CUs
   const uint64_t npkt = (uint64_t)count * esz / kPacket;
-  const Cfg c = oneshot_cfg(dtype, cfg, npkt, (uint64_t)count * esz, n, -1);
+  const Cfg c = oneshot_cfg(dtype, op, cfg, npkt, (uint64_t)count * esz, n, -1);
   // the same refusals as hiccl_reduce_ex: a shape no kernel has is an error
   const bool has = n > kMaxArgInputs ? plan_shape_error(c, dtype).empty() : single_for(dtype, c) != nullptr;
   if (!has) return fail(hipErrorInvalidValue, "auto_choice: no kernel for this config and dtype");
@@ -145,6 +152,12 @@ int hiccl_reduce_auto_choice_ex(int dtype, const hiccl_reduce_config_t *cfg, siz
   if (dynamic) *dynamic = L.dynamic ? 1 : 0;
   if (store_policy) *store_policy = c.store + 1;
   return 0;
+}
+
+int hiccl_reduce_auto_choice_ex(int dtype, const hiccl_reduce_config_t *cfg, size_t count, double n, int cus,
+                                int *engine, int *unroll, int *blocks_per_cu, int *dynamic, int *store_policy) {
+  return hiccl_reduce_auto_choice_op(dtype, HICCL_OP_SUM, cfg, count, n, cus, engine, unroll, blocks_per_cu, dynamic,
+                                     store_policy);
 }
 
 int hiccl_reduce_auto_choice(int dtype, int acc, size_t count, double n, int cus, int *engine, int *unroll,

@@ -47,7 +47,7 @@ bool sync_if_enqueued(std::atomic<bool> &enqueued) {
 }
 
 int launch_plan(PlanArgs a, int dtype, const Cfg &c, double mean_n, int dev, hipStream_t s, int pol) {
-  plan_fn fn = pick_plan(dtype, c.acc, c.engine, c.unroll, pol);
+  plan_fn fn = pick_plan(dtype, c.acc, c.op, c.engine, c.unroll, pol);
   if (!fn)
     return fail(hipErrorInvalidValue, pol == kDefPol ? "plan: unsupported dtype / shape"
                                                      : "plan: no peer-policy kernel for this shape (PHASE default, "
@@ -89,6 +89,7 @@ void plan_quiesce(hiccl_reduce_plan *p) {
 // packets of packet-weighted mean `mean_n` inputs.
 Cfg plan_cfg(const hiccl_reduce_plan *p, uint64_t npkt, double mean_n) {
   Cfg c = resolve(&p->req);
+  c.op = p->op;
   const bool auto_unroll = !c.unroll;
   // AUTO's engine rules follow the store form the launches take by size
   c.wt = c.store_auto && plan_store_peer(p);
@@ -141,6 +142,7 @@ int plan_upload(hiccl_reduce_plan *p, hipStream_t s) {
 
 int plan_kernel(hiccl_reduce_plan *p, hipStream_t s) {
   Cfg c = resolve(&p->req);
+  c.op = p->op;
   c.engine = p->engine;
   c.unroll = p->unroll;
   c.block = p->engine == HICCL_ENGINE_PHASE ? kPhBlock : kDefBlock;
@@ -163,6 +165,7 @@ int plan_set_field(hiccl_reduce_plan_t *p, int hiccl_reduce_config_t::*field, in
   hiccl_reduce_config_t c = p->req;
   c.*field = value;
   if (int e = check_cfg(&c, who)) return e;
+  if (int e = check_op(p->dtype, c.acc, p->op, who)) return e;
   p->req = c;
   p->dirty = true;  // (the auto engine's chunk size depends on the accumulator, too)
   return 0;
@@ -195,6 +198,16 @@ int hiccl_reduce_plan_set_acc(hiccl_reduce_plan_t *p, int acc) {
   return plan_set_field(p, &hiccl_reduce_config_t::acc, acc, "plan_set_acc");
 }
 
+int hiccl_reduce_plan_set_op(hiccl_reduce_plan_t *p, int op) {
+  if (!p) return fail(hipErrorInvalidValue, "plan_set_op: plan is NULL");
+  if (int e = check_op(p->dtype, p->req.acc, op, "plan_set_op")) return e;
+  p->op = op;
+  p->dirty = true;  // (AUTO's shape depends on the operator: MAX and MIN are untuned)
+  return 0;
+}
+
+int hiccl_reduce_plan_op(const hiccl_reduce_plan_t *p) { return p ? p->op : -1; }
+
 int hiccl_reduce_plan_set_engine(hiccl_reduce_plan_t *p, int engine) {
   return plan_set_field(p, &hiccl_reduce_config_t::engine, engine, "plan_set_engine");
 }
@@ -221,8 +234,10 @@ int hiccl_reduce_plan_set_config(hiccl_reduce_plan_t *p, const hiccl_reduce_conf
   memset(&z, 0, sizeof(z));
   const hiccl_reduce_config_t &c = cfg ? *cfg : z;
   if (int e = check_cfg(&c, "plan_set_config")) return e;
+  if (int e = check_op(p->dtype, c.acc, p->op, "plan_set_config")) return e;
   // the shape must be one the plan kernels have, whatever engine AUTO picks
   Cfg r = resolve(&c);
+  r.op = p->op;
   const bool shape = c.block || c.unroll;
   if (shape && r.engine == HICCL_ENGINE_AUTO) r.engine = HICCL_ENGINE_TILE;
   const int engines[2] = {HICCL_ENGINE_TILE, HICCL_ENGINE_PHASE};
@@ -289,7 +304,7 @@ int hiccl_reduce_plan_launch_each(hiccl_reduce_plan_t *p, void *stream) {
   // One one-shot launch per compute, each with the engine AUTO picks for that
   // compute alone (the reference's structure, compute.h:88-91).
   for (auto &c : p->comps)
-    if (int e = hiccl_reduce_ex(p->dtype, c.out, c.in.data(), (int)c.in.size(), c.count, stream, &p->req))
+    if (int e = hiccl_reduce_op(p->dtype, p->op, c.out, c.in.data(), (int)c.in.size(), c.count, stream, &p->req))
       return e;
   p->launched = true;
   p->last = (hipStream_t)stream;

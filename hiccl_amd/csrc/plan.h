@@ -11,6 +11,7 @@
 struct hiccl_reduce_plan {
   int dtype = 0;
   int device = 0;
+  int op = HICCL_OP_SUM;          // hiccl_reduce_plan_set_op
   hiccl_reduce_config_t req;      // hiccl_reduce_plan_set_config / _set_engine / _set_acc (0 = default)
   int engine = HICCL_ENGINE_TILE;  // resolved at upload
   int unroll = hiccl_impl::kDefUnroll;  // TILE packets per lane, resolved at upload

@@ -8,6 +8,12 @@
 // v_pk_add_f16 per two elements).  None of the thresholds below has been
 // measured for f16; DESIGN.md section 5 (M17) records the one f16 / bf16
 // comparison.
+//
+// MAX and MIN (hiccl_op_t) are untuned under every dtype: tuned_type answers
+// false for them, so they take no wide or half-size tile and none of the
+// rules made for the tuned types; every other rule applies by dtype
+// unchanged.  No threshold below has been measured for MAX or MIN; DESIGN.md
+// section 5 (M18) records the one MAX / SUM comparison.
 #include "policy.h"
 
 namespace hiccl_impl {
@@ -72,7 +78,7 @@ uint32_t default_grab(int engine, double n, int unroll = kDefUnroll) {
 // (pick_single): a caller that asks for another block or cache policy keeps
 // the u4 / PHASE choice instead of an unsupported shape.
 int auto_wide_unroll(uint64_t npkt, double n, int dtype, const Cfg &c, int dev) {
-  if (!tuned_type(dtype, c.acc) || n < 1.5 || n >= kDynMinInputs) return 0;
+  if (!tuned_type(dtype, c.acc, c.op) || n < 1.5 || n >= kDynMinInputs) return 0;
   if ((c.block && c.block != kDefBlock) || c.nt != kDefPol % 10 || c.store != kDefPol / 10) return 0;
   if (npkt / ((uint64_t)kDefBlock * kWideUnroll) < kWideMinTicketsPerWG * (uint64_t)device_cus(dev)) return 0;
   return n < 2.5 ? 2 * kWideUnroll : kWideUnroll;
@@ -102,7 +108,7 @@ int auto_engine(uint64_t npkt, double n, int dtype, const Cfg &c, int dev) {
   // launch actually takes (by size, where a write-through kernel exists).
   const bool wt = c.wt;
   const bool wt_f32 = wt && dtype == HICCL_FLOAT32;
-  const bool wt_many = wt && tuned_type(dtype, acc);
+  const bool wt_many = wt && tuned_type(dtype, acc, c.op);
   if (n >= kDynMinInputs && packed_ok && !wt_many) {
     const uint64_t tickets = npkt / ((uint64_t)kDefBlock * kDefUnroll) / default_grab(HICCL_ENGINE_TILE, n);
     if (tickets >= kTileMinTicketsPerWG * (uint64_t)device_cus(dev)) return HICCL_ENGINE_TILE;
@@ -162,8 +168,8 @@ int auto_bpc(int engine, uint64_t npkt, int dtype, int acc, int dev) {
 // tiles on twice the workgroups finish it sooner (the C5 step, four n = 2
 // and one n = 4 computes of 2^18 f32: 4.75 vs 5.32 us queued,
 // profiles/r02c_plan_sweep.jsonl); 2 exists for the headline types only.
-int auto_unroll(uint64_t npkt, int dtype, int acc, int dev) {
-  return tuned_type(dtype, acc) && npkt < 2ull * device_cus(dev) * kDefBlock * kDefUnroll ? 2 : kDefUnroll;
+int auto_unroll(uint64_t npkt, int dtype, const Cfg &c, int dev) {
+  return tuned_type(dtype, c.acc, c.op) && npkt < 2ull * device_cus(dev) * kDefBlock * kDefUnroll ? 2 : kDefUnroll;
 }
 
 }  // namespace
@@ -204,6 +210,16 @@ int check_cfg(const hiccl_reduce_config_t *c, const std::string &who) {
   return 0;
 }
 
+int check_op(int dtype, int acc, int op, const std::string &who) {
+  if (op < HICCL_OP_SUM || op > HICCL_OP_MIN)
+    return fail(hipErrorInvalidValue, who + ": unknown op " + std::to_string(op));
+  if (op == HICCL_OP_SUM) return 0;
+  if (dtype == HICCL_BYTES) return fail(hipErrorInvalidValue, who + ": HICCL_BYTES copies take HICCL_OP_SUM only");
+  if (acc == HICCL_ACC_WIDE)
+    return fail(hipErrorInvalidValue, who + ": HICCL_ACC_WIDE is a rounding mode of sums (HICCL_OP_SUM only)");
+  return 0;
+}
+
 // nt stores are not write-through: a launch's output lines may sit dirty in
 // the XCD L2s until the end-of-kernel release writes them back, on the
 // critical path of the next kernel on the stream (MI355X_MICROARCH.md
@@ -240,7 +256,7 @@ void finish_cfg(Cfg &c, uint64_t npkt, double n, int dtype, int dev) {
     if (!c.block) c.block = kDefBlock;
     if (!c.unroll) {
       const int wide = auto_wide_unroll(npkt, n, dtype, c, dev);
-      c.unroll = wide ? wide : auto_unroll(npkt, dtype, c.acc, dev);
+      c.unroll = wide ? wide : auto_unroll(npkt, dtype, c, dev);
     }
   }
   if (!c.bpc) c.bpc = auto_bpc(c.engine, npkt, dtype, c.acc, dev);
@@ -252,16 +268,17 @@ void finish_cfg(Cfg &c, uint64_t npkt, double n, int dtype, int dev) {
 // again for them.  n > 64 inputs run on the plan kernel (reduce_via_table),
 // whose kernels decide.  hiccl_reduce_ex and hiccl_reduce_auto_choice_ex
 // share it.
-Cfg oneshot_cfg(int dtype, const hiccl_reduce_config_t *cfg, uint64_t npkt, uint64_t out_bytes, double n,
+Cfg oneshot_cfg(int dtype, int op, const hiccl_reduce_config_t *cfg, uint64_t npkt, uint64_t out_bytes, double n,
                 int dev) {
-  const Cfg raw = resolve(cfg);
+  Cfg raw = resolve(cfg);
+  raw.op = op;
   Cfg c = raw;
   c.wt = wt_by_size(raw, dtype, n, out_bytes);
   finish_cfg(c, npkt, n, dtype, dev);
   if (!c.wt) return c;
   Cfg w = c;
   w.store = kPolStoreSys;
-  if (n > kMaxArgInputs ? pick_plan(dtype, w.acc, w.engine, w.unroll, plan_pol(HICCL_PEER_STORES)) != nullptr
+  if (n > kMaxArgInputs ? pick_plan(dtype, w.acc, w.op, w.engine, w.unroll, plan_pol(HICCL_PEER_STORES)) != nullptr
                         : single_for(dtype, w) != nullptr)
     return w;
   c = raw;
@@ -295,7 +312,7 @@ std::string plan_shape_error(const Cfg &c, int dtype) {
   const bool wt = c.store == kPolStoreSys;
   if (wt && !wt_unroll(c.unroll))
     return "write-through plan kernels (store_policy 4) run the TILE engine at unroll 4 (f32 / bf16 / f16: 2 or 4) only";
-  if (!pick_plan(dtype, c.acc, HICCL_ENGINE_TILE, c.unroll, plan_pol(wt ? HICCL_PEER_STORES : 0)))
+  if (!pick_plan(dtype, c.acc, c.op, HICCL_ENGINE_TILE, c.unroll, plan_pol(wt ? HICCL_PEER_STORES : 0)))
     return "plan kernels run the TILE engine at unroll 4 (f32 / bf16 / f16: 1, 2, 4, 8 or 16) only";
   return "";
 }

@@ -15,6 +15,7 @@ struct Cfg {
   bool wt;          // the launch stores write-through by size: decided BEFORE the engine
                     // (oneshot_cfg, plan_cfg), since AUTO's engine rules differ under it
   int order;        // tile-order segments (hiccl_reduce_config_t.order; 0/1 linear)
+  int op;           // hiccl_op_t: not a config entry -- the call or the plan names it (resolve: SUM)
   int pol() const { return store * 10 + nt; }
 };
 
@@ -24,6 +25,9 @@ Cfg resolve(const hiccl_reduce_config_t *c);
 // The enumerated and ranged fields of a caller's config (NULL: all
 // defaults), refused as `who: ...` with hipErrorInvalidValue.
 int check_cfg(const hiccl_reduce_config_t *c, const std::string &who);
+// An operator for this dtype and accumulation mode: known, and SUM for
+// HICCL_BYTES and HICCL_ACC_WIDE.  Refused as `who: ...` likewise.
+int check_op(int dtype, int acc, int op, const std::string &who);
 
 // Does a launch that writes `out_bytes` from `n` inputs per output (a plan's
 // packet-weighted mean) store write-through BY SIZE under the raw config?
@@ -36,10 +40,11 @@ inline bool wt_unroll(int unroll) { return unroll == 2 || unroll == kDefUnroll; 
 void finish_cfg(Cfg &c, uint64_t npkt, double n, int dtype, int dev);
 
 // The one-shot call's configuration, engine and store form resolved.
-Cfg oneshot_cfg(int dtype, const hiccl_reduce_config_t *cfg, uint64_t npkt, uint64_t out_bytes, double n, int dev);
+Cfg oneshot_cfg(int dtype, int op, const hiccl_reduce_config_t *cfg, uint64_t npkt, uint64_t out_bytes, double n,
+                int dev);
 // Its kernel (n <= kMaxArgInputs), or NULL.
 inline single_fn single_for(int dtype, const Cfg &c) {
-  return pick_single(dtype, c.acc, c.engine, c.block, c.unroll, c.pol());
+  return pick_single(dtype, c.acc, c.op, c.engine, c.block, c.unroll, c.pol());
 }
 
 // The plan kernels' cache policy: nt loads and stores, or a plan's peer

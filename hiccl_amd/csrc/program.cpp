@@ -14,6 +14,8 @@ using namespace hiccl_impl;
 struct hiccl_program {
   int dtype = 0;
   int device = 0;
+  int op = HICCL_OP_SUM;  // the first reducing plan's (hiccl_program_add_plan)
+  bool has_op = false;    // a reducing plan has been added
   struct Unit {
     void *out;
     std::vector<const void *> in;
@@ -73,7 +75,7 @@ int prog_upload(hiccl_program *p, hipStream_t s) {
   // half-size tiles when the batch has under two 16 KiB tiles per CU (as a
   // plan's auto unroll)
   const bool small = total_pkt < 2ull * cus * kProgBlock * 4;
-  p->unroll = pick_prog(p->dtype, 2) && small ? 2 : 4;
+  p->unroll = pick_prog(p->dtype, p->op, 2) && small ? 2 : 4;
   DescTable t(maxn, (uint64_t)kProgBlock * p->unroll);
   for (auto &u : p->units)
     t.add(u.out, u.in.data(), u.in.size(), u.count, esz_of(u), (u.bytes ? 1u : 0u) | ((uint32_t)u.peer << 1));
@@ -132,7 +134,7 @@ extern "C" {
 int hiccl_program_create(hiccl_program_t **prog, int dtype, int device) {
   if (!prog) return fail(hipErrorInvalidValue, "program_create: prog is NULL");
   *prog = nullptr;
-  if (!pick_prog(dtype, 4)) return fail(hipErrorInvalidValue, "program_create: unsupported dtype");
+  if (!pick_prog(dtype, HICCL_OP_SUM, 4)) return fail(hipErrorInvalidValue, "program_create: unsupported dtype");
   int ndev = 0;
   if (int e = check_hip(hipGetDeviceCount(&ndev), "program_create: hipGetDeviceCount")) return e;
   if (device < 0 || device >= ndev) return fail(hipErrorInvalidDevice, "program_create: bad device");
@@ -171,6 +173,15 @@ int hiccl_program_add_plan(hiccl_program_t *p, const hiccl_reduce_plan_t *plan) 
     return fail(hipErrorInvalidValue, "program_add_plan: the plan's dtype is neither the program's nor HICCL_BYTES");
   if (plan->req.acc == HICCL_ACC_WIDE)
     return fail(hipErrorInvalidValue, "program_add_plan: programs accumulate natively (HICCL_ACC_NATIVE) only");
+  if (!bytes) {
+    if (p->has_op && plan->op != p->op)
+      return fail(hipErrorInvalidValue,
+                  "program_add_plan: the plan's op differs from the op of the program's first reducing plan");
+    if (!pick_prog(p->dtype, plan->op, 4))
+      return fail(hipErrorInvalidValue, "program_add_plan: no program kernel for this dtype and op");
+    p->op = plan->op;
+    p->has_op = true;
+  }
   const int peer = plan_eff_peer(plan);  // the plan's own store form (wt_by_size) carries over
   for (auto &c : plan->comps) p->units.push_back(hiccl_program::Unit{c.out, c.in, c.count, bytes, peer});
   p->dirty = true;
@@ -196,7 +207,7 @@ int hiccl_program_launch(hiccl_program_t *p, const uint32_t *epochs, const uint3
   if (p->phases.empty() && p->units.empty()) return 0;
   hipStream_t s = (hipStream_t)stream;
   if (int e = prog_upload(p, s)) return e;
-  prog_fn fn = pick_prog(p->dtype, p->unroll);
+  prog_fn fn = pick_prog(p->dtype, p->op, p->unroll);
   if (!fn) return fail(hipErrorInvalidValue, "program_launch: no kernel for this dtype / shape");
   ProgArgs a = p->args;
   a.err = err;

@@ -33,689 +33,15 @@
 //
 // Layout / roofline / measured numbers: DESIGN.md.
 //
-// This file is the device code and its kernel tables only.  The host files
-// (policy.cpp: the AUTO rules; oneshot.cpp, plan.cpp, ...: the C ABI) see it
-// through kernels.h.
+// The engines and kernels are templates in engine.h.  This file instantiates
+// them for the SUM ops and holds the plain kernels (fills, copies, stream
+// signalling); reduce_ops.hip instantiates them for MAX and MIN.  The host
+// files (policy.cpp: the AUTO rules; oneshot.cpp, plan.cpp, ...: the C ABI)
+// see both through kernels.h.
 
-#include <hip/hip_runtime.h>
-
-#include <stdint.h>
-
-#include <type_traits>
-
-#include "../../include/hiccl_reduce.h"
-#include "kernels.h"
-
-using namespace hiccl_impl;
+#include "engine.h"
 
 namespace {
-
-// ------------------------------------------------------------ vector types --
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-// 16-byte packet type with 1-byte alignment: a misaligned input still loads
-// as one global_load_dwordx4 (gfx950 unaligned access mode).
-typedef uint32_t u32x4u __attribute__((ext_vector_type(4), aligned(1)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef double f64x2 __attribute__((ext_vector_type(2)));
-typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
-typedef float f32x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-
-// Buffer resources: one SGPR descriptor per input per tile (base = input +
-// tile offset, range = the tile's valid bytes).  Loads/stores then take only
-// the tile-invariant 32-bit lane offset, and the hardware range check turns
-// the lanes past the end of the last (partial) tile into no-ops.
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
-constexpr int kRsrcFlags = 0x00020000;  // raw buffer, 32-bit data format
-
-__device__ __forceinline__ rsrc_t make_rsrc(const char *base, uint32_t nbytes) {
-  return __builtin_amdgcn_make_buffer_rsrc((void *)base, (short)0, (int)nbytes, kRsrcFlags);
-}
-
-// Cache policy POL = 10*store + load: kernels.h.
-template <int POL>
-__device__ __forceinline__ u32x4 load_pkt(rsrc_t r, uint32_t voff) {
-  constexpr int lp = POL % 10;
-  return __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, 0, lp == 1 ? 2 : lp == kPolLoadSys ? 17 : 0);
-}
-
-template <int POL>
-__device__ __forceinline__ void store_pkt(rsrc_t r, uint32_t voff, u32x4 v) {
-  constexpr int sp = POL / 10;
-  __builtin_amdgcn_raw_buffer_store_b128(v, r, (int)voff, 0, sp == 1 ? 2 : sp == 2 ? 16 : sp == kPolStoreSys ? 17 : 0);
-}
-
-// bf16 <-> f32.  f32 -> bf16 is round-to-nearest-even; on gfx950 the cast
-// lowers to v_cvt_pk_bf16_f32, which keeps a NaN a NaN.
-__device__ __forceinline__ float bf_lo(uint32_t w) { return __uint_as_float(w << 16); }
-__device__ __forceinline__ float bf_hi(uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
-__device__ __forceinline__ uint32_t bf_pack(float lo, float hi) {
-  bf16x2 v = {(__bf16)lo, (__bf16)hi};
-  return __builtin_bit_cast(uint32_t, v);
-}
-__device__ __forceinline__ uint16_t bf_round(float f) {
-  return __builtin_bit_cast(uint16_t, (__bf16)f);
-}
-
-// Scalar head/tail accesses through the GLOBAL address space: a generic
-// pointer becomes a flat access, and a flat load pending anywhere inside the
-// plan kernel's unit loop makes the waitcnt pass treat vmcnt as out of order
-// -- every tile's adds then waited with vmcnt(0) instead of a staircase.
-template <class T>
-__device__ __forceinline__ T gld(const char *p) {
-  return *(const __attribute__((address_space(1))) T *)p;
-}
-template <class T>
-__device__ __forceinline__ void gst(char *p, T v) {
-  *(__attribute__((address_space(1))) T *)p = v;
-}
-
-// ------------------------------------------------------------ element ops --
-// Each op: elem size, packet accumulator (acc_t) with zero/add/pack, and a
-// scalar accumulator for the peeled head/tail elements.  zero() + x keeps the
-// reference's `T acc = 0; acc += x` (so -0 inputs sum to +0).
-
-struct OpF32 {
-  static constexpr bool kWidens = false;
-  static constexpr int kEsz = 4;
-  typedef f32x4 acc_t;
-  __device__ static acc_t zero() { return (f32x4)(0.0f); }
-  __device__ static acc_t add(acc_t a, u32x4 p) { return a + __builtin_bit_cast(f32x4, p); }
-  __device__ static u32x4 pack(acc_t a) { return __builtin_bit_cast(u32x4, a); }
-  typedef float sacc_t;
-  __device__ static sacc_t szero() { return 0.0f; }
-  __device__ static sacc_t sadd(sacc_t a, const char *p) { return a + gld<float>(p); }
-  __device__ static void sstore(char *p, sacc_t a) { gst<float>(p, a); }
-};
-
-struct OpF64 {
-  static constexpr bool kWidens = false;
-  static constexpr int kEsz = 8;
-  typedef f64x2 acc_t;
-  __device__ static acc_t zero() { return (f64x2)(0.0); }
-  __device__ static acc_t add(acc_t a, u32x4 p) { return a + __builtin_bit_cast(f64x2, p); }
-  __device__ static u32x4 pack(acc_t a) { return __builtin_bit_cast(u32x4, a); }
-  typedef double sacc_t;
-  __device__ static sacc_t szero() { return 0.0; }
-  __device__ static sacc_t sadd(sacc_t a, const char *p) { return a + gld<double>(p); }
-  __device__ static void sstore(char *p, sacc_t a) { gst<double>(p, a); }
-};
-
-struct OpU64 {
-  static constexpr bool kWidens = false;
-  static constexpr int kEsz = 8;
-  typedef u64x2 acc_t;
-  __device__ static acc_t zero() { return (u64x2)(0); }
-  __device__ static acc_t add(acc_t a, u32x4 p) { return a + __builtin_bit_cast(u64x2, p); }
-  __device__ static u32x4 pack(acc_t a) { return __builtin_bit_cast(u32x4, a); }
-  typedef uint64_t sacc_t;
-  __device__ static sacc_t szero() { return 0; }
-  __device__ static sacc_t sadd(sacc_t a, const char *p) { return a + gld<uint64_t>(p); }
-  __device__ static void sstore(char *p, sacc_t a) { gst<uint64_t>(p, a); }
-};
-
-struct OpI32 {  // two's-complement wrap-around, done in unsigned
-  static constexpr bool kWidens = false;
-  static constexpr int kEsz = 4;
-  typedef u32x4 acc_t;
-  __device__ static acc_t zero() { return (u32x4)(0u); }
-  __device__ static acc_t add(acc_t a, u32x4 p) { return a + p; }
-  __device__ static u32x4 pack(acc_t a) { return a; }
-  typedef uint32_t sacc_t;
-  __device__ static sacc_t szero() { return 0u; }
-  __device__ static sacc_t sadd(sacc_t a, const char *p) { return a + gld<uint32_t>(p); }
-  __device__ static void sstore(char *p, sacc_t a) { gst<uint32_t>(p, a); }
-};
-
-// bf16, reference semantics: acc is bf16, every add = f32 add then round to
-// bf16.  The accumulator is kept PACKED (8 bf16 in a u32x4, the packet's own
-// layout): widen both operands (exact), add in f32, round-to-nearest-even
-// back (v_cvt_pk_bf16_f32).  4 VGPRs per packet, so the phased engine runs
-// bf16 at the same 128 KiB chunk as f32.
-// The pack is an opaque v_cvt_pk_bf16_f32 (the same instruction the __bf16
-// casts lower to) so the compiler cannot see through pack->widen and keep the
-// accumulator widened in 8 VGPRs per packet (it does, and spills).
-__device__ __forceinline__ uint32_t bf_pack_opaque(float lo, float hi) {
-  uint32_t r;
-  asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-  return r;
-}
-
-struct OpBF16 {
-  static constexpr bool kWidens = true;
-  static constexpr int kEsz = 2;
-  typedef u32x4 acc_t;
-  __device__ static acc_t zero() { return (u32x4)(0u); }  // +0 bf16
-  __device__ static acc_t add(acc_t a, u32x4 p) {
-    acc_t r;
-#pragma unroll
-    for (int w = 0; w < 4; w++)
-      r[w] = bf_pack_opaque(bf_lo(a[w]) + bf_lo(p[w]), bf_hi(a[w]) + bf_hi(p[w]));
-    return r;
-  }
-  __device__ static u32x4 pack(acc_t a) { return a; }
-  typedef float sacc_t;
-  __device__ static sacc_t szero() { return 0.0f; }
-  __device__ static sacc_t sadd(sacc_t a, const char *p) {
-    float s = a + __uint_as_float((uint32_t)(gld<uint16_t>(p)) << 16);
-    return __uint_as_float((uint32_t)bf_round(s) << 16);
-  }
-  __device__ static void sstore(char *p, sacc_t a) { gst<uint16_t>(p, bf_round(a)); }
-};
-
-// bf16 inputs, f32 accumulator, one rounding at the end (HICCL_ACC_WIDE).
-struct OpBF16Wide {
-  static constexpr bool kWidens = true;
-  static constexpr int kEsz = 2;
-  typedef f32x8 acc_t;
-  __device__ static acc_t zero() { return (f32x8)(0.0f); }
-  __device__ static acc_t add(acc_t a, u32x4 p) {
-#pragma unroll
-    for (int w = 0; w < 4; w++) {
-      a[2 * w] += bf_lo(p[w]);
-      a[2 * w + 1] += bf_hi(p[w]);
-    }
-    return a;
-  }
-  __device__ static u32x4 pack(acc_t a) {
-    u32x4 r;
-#pragma unroll
-    for (int w = 0; w < 4; w++) r[w] = bf_pack(a[2 * w], a[2 * w + 1]);
-    return r;
-  }
-  typedef float sacc_t;
-  __device__ static sacc_t szero() { return 0.0f; }
-  __device__ static sacc_t sadd(sacc_t a, const char *p) {
-    return a + __uint_as_float((uint32_t)(gld<uint16_t>(p)) << 16);
-  }
-  __device__ static void sstore(char *p, sacc_t a) { gst<uint16_t>(p, bf_round(a)); }
-};
-
-// fp16 (IEEE half), reference semantics: acc is half and every add is a half
-// add.  gfx950 has that add natively -- one v_pk_add_f16 adds two elements,
-// rounded to nearest even, subnormals kept (the code object's 16-bit denorm
-// mode) -- so the accumulator stays in the packet's own layout (4 VGPRs) and
-// an add costs four instructions per packet, with no widen / round pair.
-typedef _Float16 half_t;
-__device__ __forceinline__ half_t f16_ld(const char *p) { return __builtin_bit_cast(half_t, gld<uint16_t>(p)); }
-__device__ __forceinline__ float f16_widen(uint32_t w, int hi) {
-  return (float)__builtin_bit_cast(f16x2, w)[hi];
-}
-// f32 -> half is round-to-nearest-even (v_cvt_f16_f32); overflow gives Inf
-// and a NaN stays a NaN.
-__device__ __forceinline__ uint16_t f16_round(float f) { return __builtin_bit_cast(uint16_t, (half_t)f); }
-
-struct OpF16 {
-  static constexpr bool kWidens = false;
-  static constexpr int kEsz = 2;
-  typedef f16x8 acc_t;
-  __device__ static acc_t zero() { return (f16x8)((half_t)0.0f); }  // +0
-  __device__ static acc_t add(acc_t a, u32x4 p) { return a + __builtin_bit_cast(f16x8, p); }
-  __device__ static u32x4 pack(acc_t a) { return __builtin_bit_cast(u32x4, a); }
-  typedef half_t sacc_t;
-  __device__ static sacc_t szero() { return (half_t)0.0f; }
-  __device__ static sacc_t sadd(sacc_t a, const char *p) { return a + f16_ld(p); }
-  __device__ static void sstore(char *p, sacc_t a) { gst<uint16_t>(p, __builtin_bit_cast(uint16_t, a)); }
-};
-
-// fp16 inputs, f32 accumulator, one rounding at the end (HICCL_ACC_WIDE): a
-// sequential f32 sum in input order from +0, NOT reference-bitwise.
-struct OpF16Wide {
-  static constexpr bool kWidens = true;
-  static constexpr int kEsz = 2;
-  typedef f32x8 acc_t;
-  __device__ static acc_t zero() { return (f32x8)(0.0f); }
-  __device__ static acc_t add(acc_t a, u32x4 p) {
-#pragma unroll
-    for (int w = 0; w < 4; w++) {
-      a[2 * w] += f16_widen(p[w], 0);
-      a[2 * w + 1] += f16_widen(p[w], 1);
-    }
-    return a;
-  }
-  __device__ static u32x4 pack(acc_t a) {
-    u32x4 r;
-#pragma unroll
-    for (int w = 0; w < 4; w++) {
-      f16x2 v = {(half_t)a[2 * w], (half_t)a[2 * w + 1]};
-      r[w] = __builtin_bit_cast(uint32_t, v);
-    }
-    return r;
-  }
-  typedef float sacc_t;
-  __device__ static sacc_t szero() { return 0.0f; }
-  __device__ static sacc_t sadd(sacc_t a, const char *p) { return a + (float)f16_ld(p); }
-  __device__ static void sstore(char *p, sacc_t a) { gst<uint16_t>(p, f16_round(a)); }
-};
-
-// Exact byte copy (HICCL_BYTES): one input, out = in[0] bit for bit.  The
-// transport's batched data movement runs on the same tile engine.
-struct OpRaw {
-  static constexpr bool kWidens = false;
-  static constexpr int kEsz = 1;
-  typedef u32x4 acc_t;
-  __device__ static acc_t zero() { return (u32x4)(0u); }
-  __device__ static acc_t add(acc_t, u32x4 p) { return p; }
-  __device__ static u32x4 pack(acc_t a) { return a; }
-  typedef uint8_t sacc_t;
-  __device__ static sacc_t szero() { return 0; }
-  __device__ static sacc_t sadd(sacc_t, const char *p) { return gld<uint8_t>(p); }
-  __device__ static void sstore(char *p, sacc_t a) { gst<uint8_t>(p, a); }
-};
-
-// ----------------------------------------------------------- tile engine --
-//
-// A compute is split as [head scalars | npkt 16-B packets | tail scalars],
-// the packets 16-B aligned on the OUTPUT.  A tile = BLOCK*U packets; lane t
-// of the workgroup owns packets u*BLOCK + t (u < U), so every load
-// instruction of a wave covers 1 KiB contiguous bytes of one input.
-// (SingleArgs, PlanDesc, PlanArgs: kernels.h.)
-
-// Input pointer source: kernarg array or device table.
-struct ArgInputs {
-  const char *const *p;
-  __device__ const char *operator()(int k) const { return p[k]; }
-};
-
-// Under the peer policies the plain scalar accesses are bracketed by
-// system-scope fences instead (an acquire before the loads: this XCD's L2
-// drops lines of peer memory; a release after the stores: its dirty lines
-// are written back) -- only the workgroup owning a compute's first unit,
-// and only when the compute has a head or a tail.
-template <class Op, int POL = 11, class Inputs>
-__device__ __forceinline__ void scalar_part(char *out, Inputs in, uint32_t n, uint32_t head,
-                                            uint64_t npkt, uint32_t tail, int tid) {
-  constexpr int V = kPacket / Op::kEsz;
-  if (tid >= (int)(head + tail)) return;
-  if constexpr (POL % 10 == kPolLoadSys) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
-  uint64_t e = (tid < (int)head) ? (uint64_t)tid : (uint64_t)head + npkt * V + (tid - head);
-  uint64_t off = e * Op::kEsz;
-  typename Op::sacc_t acc = Op::szero();
-  for (uint32_t k = 0; k < n; k++) acc = Op::sadd(acc, in(k) + off);
-  Op::sstore(out + off, acc);
-  if constexpr (POL / 10 == kPolStoreSys) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
-}
-
-// One group of G inputs (G static): G descriptor builds (scalar), then G*U
-// independent 16-B buffer loads, then the G in-order adds per packet.
-//
-// PACED: a pause of kPaceSleep x 64 clocks between one input's U loads and the
-// next input's.  With scalar descriptors the G*U loads of a wave issue back to
-// back, and on the one launch that is bound by HBM alone -- config 2's
-// one-shot tiles on the ticket counter, 256 workgroups x 4 waves bursting 32
-// KiB each -- that burst measured 1.1-1.6 % SLOWER than the waterfall loops
-// it replaced, which had spread the same loads over about a microsecond.
-// Spreading them on purpose gives that back, and on 7/8 of the grid
-// (policy.cpp launch_shape) runs 2.4 % ahead.  The
-// pauses hide under the tile's memory time; a latency-bound launch (static
-// schedule, plans, programs) would pay for them, so only the one-shot
-// kernel's dynamic schedule asks for them.
-constexpr int kPaceSleep = 4;
-
-template <class Op, int U, int G, int POL, bool PACED, class Inputs>
-__device__ __forceinline__ void group_at(typename Op::acc_t (&acc)[U], Inputs in, uint32_t g,
-                                         uint64_t tile_off, uint32_t tile_bytes,
-                                         const uint32_t (&voff)[U]) {
-  rsrc_t r[G];
-#pragma unroll
-  for (int j = 0; j < G; j++) r[j] = make_rsrc(in(g + j) + tile_off, tile_bytes);
-  u32x4 x[G][U];
-  // Every load of the group is issued before the first add, input by input
-  // (the barriers pin that order, so the adds -- input 0 first -- wait with
-  // a vmcnt staircase instead of one vmcnt(0)).  Without them the scheduler
-  // of the plan kernel (pointer table in memory) split an 8-input group into
-  // 24 + 8 (f32) or 16 + 16 (bf16) loads with an s_waitcnt vmcnt(0) in
-  // between: two memory round trips per tile.
-#pragma unroll
-  for (int j = 0; j < G; j++) {
-#pragma unroll
-    for (int u = 0; u < U; u++) x[j][u] = load_pkt<POL>(r[j], voff[u]);
-    __builtin_amdgcn_sched_barrier(0);
-    if constexpr (PACED) {
-      if (j + 1 < G) {
-        __builtin_amdgcn_s_sleep(kPaceSleep);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < G; j++) {
-#pragma unroll
-    for (int u = 0; u < U; u++) acc[u] = Op::add(acc[u], x[j][u]);
-  }
-}
-
-// One tile: packets pkt0 + u*BLOCK + tid, tile_bytes = valid bytes of the
-// tile (< the full tile only for the last one).  Inputs are consumed as full
-// groups of 8 followed by one statically sized remainder group, so the adds
-// happen in exactly the order k = 0, 1, ..., n-1.
-// `before_store()` runs after the last add, before the stores (the unit
-// scheduler publishes its next ticket there: every load has been waited for
-// and no store is pending yet, so reading the atomic's result costs nothing).
-struct NoHook {
-  static constexpr bool kDynamic = false;
-  __device__ void operator()() const {}
-};
-
-template <class Op, int U, int POL, bool PACED = false, class Inputs, class Hook = NoHook>
-__device__ __forceinline__ void tile_body(char *outb, Inputs in, uint32_t n, uint64_t tile_off,
-                                          uint32_t tile_bytes, const uint32_t (&voff)[U],
-                                          Hook before_store = Hook()) {
-  typename Op::acc_t acc[U];
-#pragma unroll
-  for (int u = 0; u < U; u++) acc[u] = Op::zero();
-  // The output's descriptor is built here, ahead of the input groups, and not
-  // next to the stores: built behind the switch below, the u64 kernels got it
-  // as a VGPR copy joined over the switch's cases, and with it a waterfall
-  // loop around each of their stores (4 SGPRs held over the tile instead).
-  const rsrc_t w = make_rsrc(outb + tile_off, tile_bytes);
-  // groups of GM inputs: at most 32 packets per lane in flight (U = 8: 4
-  // inputs, U = 16: 2), so wide tiles stay within the register file
-  constexpr uint32_t GM = U >= 8 ? 32 / U : 8;
-  uint32_t g = 0;
-  for (; g + GM <= n; g += GM) group_at<Op, U, GM, POL, PACED>(acc, in, g, tile_off, tile_bytes, voff);
-  switch (n - g) {  // wave-uniform
-    case 1: group_at<Op, U, 1, POL, PACED>(acc, in, g, tile_off, tile_bytes, voff); break;
-    case 2: if constexpr (GM > 2) group_at<Op, U, 2, POL, PACED>(acc, in, g, tile_off, tile_bytes, voff); break;
-    case 3: if constexpr (GM > 3) group_at<Op, U, 3, POL, PACED>(acc, in, g, tile_off, tile_bytes, voff); break;
-    case 4: if constexpr (GM > 4) group_at<Op, U, 4, POL, PACED>(acc, in, g, tile_off, tile_bytes, voff); break;
-    case 5: if constexpr (GM > 5) group_at<Op, U, 5, POL, PACED>(acc, in, g, tile_off, tile_bytes, voff); break;
-    case 6: if constexpr (GM > 6) group_at<Op, U, 6, POL, PACED>(acc, in, g, tile_off, tile_bytes, voff); break;
-    case 7: if constexpr (GM > 7) group_at<Op, U, 7, POL, PACED>(acc, in, g, tile_off, tile_bytes, voff); break;
-    default: break;
-  }
-  before_store();
-#pragma unroll
-  for (int u = 0; u < U; u++) store_pkt<POL>(w, voff[u], Op::pack(acc[u]));
-}
-
-// Input-phased chunk (the default engine for large buckets).  A chunk =
-// BLOCK*P packets; lane t owns packets p*BLOCK + t.  The workgroup sweeps
-// input 0 of the chunk, then input 1, ...: input j+1's P loads are in flight
-// while input j is added, so chip-wide only ~2 input streams are open at a
-// time and each is read as long contiguous runs (BLOCK*P*16 B per workgroup;
-// 128 KiB at the default 512 x 16).  The per-element add order is unchanged
-// (k = 0, 1, ..., n-1 from a zero accumulator).  Measured: the nine-stream
-// tile order runs at 5.5-5.8 TB/s and depends on the physical placement of
-// the buckets; the phased order at 6.0-6.4 TB/s.
-// n is runtime: inputs are taken in pairs; the load that would read past
-// input n-1 gets a zero-range descriptor (no memory traffic, reads 0, never
-// added).
-template <class Op, int P, int POL, class Inputs, class Hook = NoHook>
-__device__ __forceinline__ void chunk_body(char *outb, Inputs in, uint32_t n, uint64_t off,
-                                           uint32_t nbytes, const uint32_t (&voff)[P],
-                                           Hook before_store = Hook()) {
-  typename Op::acc_t acc[P];
-#pragma unroll
-  for (int p = 0; p < P; p++) acc[p] = Op::zero();
-  if (n > 0) {
-    u32x4 x[P], y[P];
-    {
-      rsrc_t r = make_rsrc(in(0) + off, nbytes);
-#pragma unroll
-      for (int p = 0; p < P; p++) x[p] = load_pkt<POL>(r, voff[p]);
-    }
-    uint32_t j = 0;
-    for (; j + 2 <= n; j += 2) {  // x: input j in flight
-      rsrc_t ry = make_rsrc(in(j + 1) + off, nbytes);
-#pragma unroll
-      for (int p = 0; p < P; p++) y[p] = load_pkt<POL>(ry, voff[p]);
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int p = 0; p < P; p++) {
-        acc[p] = Op::add(acc[p], x[p]);
-        if constexpr (Op::kWidens) __builtin_amdgcn_sched_barrier(0);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      const bool more = j + 2 < n;
-      rsrc_t rx = make_rsrc(in(more ? j + 2 : j + 1) + off, more ? nbytes : 0u);
-#pragma unroll
-      for (int p = 0; p < P; p++) x[p] = load_pkt<POL>(rx, voff[p]);
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int p = 0; p < P; p++) {
-        acc[p] = Op::add(acc[p], y[p]);
-        if constexpr (Op::kWidens) __builtin_amdgcn_sched_barrier(0);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    if (n & 1) {
-#pragma unroll
-      for (int p = 0; p < P; p++) acc[p] = Op::add(acc[p], x[p]);
-    }
-  }
-  before_store();
-  rsrc_t w = make_rsrc(outb + off, nbytes);
-#pragma unroll
-  for (int p = 0; p < P; p++) store_pkt<POL>(w, voff[p], Op::pack(acc[p]));
-}
-
-// Engines: kTile = all n inputs of a BLOCK*U tile loaded together (small
-// computes, many tiles); kPhase = chunk_body (large buckets).
-constexpr int kTile = 0;
-constexpr int kPhase = 1;
-
-// A value every lane of the workgroup holds alike, moved to SGPRs.
-__device__ __forceinline__ uint32_t uniform32(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ uint64_t uniform64(uint64_t v) {
-  return (uint64_t)uniform32((uint32_t)(v >> 32)) << 32 | uniform32((uint32_t)v);
-}
-
-// One unit of either engine.  Every kernel's units come through here, and
-// this is where a unit's two descriptor inputs -- its byte offset and its
-// valid byte count -- are made scalar, once per unit: the bodies' make_rsrc
-// then add them to kernarg / constant-memory pointers and every descriptor
-// stays in SGPRs.  Left alone they reach the bodies in VGPRs (the unit index
-// comes out of LDS on the dynamic schedule and through tile_order's branch;
-// the byte count out of a 64-bit compare/select, which gfx9 has on the VALU
-// only), and the compiler then wraps EACH buffer load and store in a
-// readfirstlane waterfall loop: ~12 instructions per memory op, one loop
-// finished before the next op issues.
-// Both values are workgroup-uniform on every path: they are functions of the
-// unit index and of kernel arguments / descriptor words read at uniform
-// addresses, and the unit index is blockIdx.x + k * gridDim.x (static
-// schedule, k_program) or a ticket that thread 0 stored to s_next[] before
-// the barrier every lane read it behind (for_each_unit).  tile_order (any
-// `order`) and the clamp of the last, partial unit are pure functions of
-// those; a scalar-only compute returns before it gets here, on a uniform
-// branch.
-template <class Op, int U, int POL, int ENG, bool PACED = false, class Inputs, class Hook = NoHook>
-__device__ __forceinline__ void unit_body(char *outb, Inputs in, uint32_t n, uint64_t off,
-                                          uint32_t nbytes, const uint32_t (&voff)[U], Hook hook = Hook()) {
-  const uint64_t uoff = uniform64(off);
-  const uint32_t ubytes = uniform32(nbytes);
-  if constexpr (ENG == kPhase)
-    chunk_body<Op, U, POL>(outb, in, n, uoff, ubytes, voff, hook);
-  else
-    tile_body<Op, U, POL, PACED>(outb, in, n, uoff, ubytes, voff, hook);
-}
-
-// Body inputs shifted by the head: base(k) = in[k] + head*esz.
-template <class Inner>
-struct Shifted {
-  Inner in;
-  uint64_t shift;
-  __device__ const char *operator()(int k) const { return in(k) + shift; }
-};
-
-// ---------------------------------------------------- unit scheduling ----
-//
-// Static: workgroup b takes units b, b + grid, ...  Dynamic (sched != NULL):
-// every workgroup takes its next unit from a device counter, so the
-// workgroups the memory system serves faster do more units and the launch's
-// tail is one unit instead of the slowest workgroup's share (+1.6-2.1 % on
-// C2: profiles/r01_phase_probe_dyn.jsonl).  The next ticket is fetched one
-// unit ahead so the atomic's latency hides under the current unit.  The
-// counter pair {ticket, done} is zero on entry; the last workgroup to finish
-// resets it, so consecutive launches on one stream (or replays of a graph)
-// reuse it without a memset.  The host gives every (device, stream) its own
-// pair and never uses it during stream capture (ticket_counter(), runtime.cpp).
-__device__ __forceinline__ void drain_stores(uint32_t drain) {
-  if (drain) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-}
-
-// The hook a unit of the dynamic schedule gets.  kDynamic lets a kernel tell
-// the two schedules apart at compile time (NoHook: the static one).
-template <class F>
-struct TicketHook {
-  static constexpr bool kDynamic = true;
-  F f;
-  __device__ void operator()() const { f(); }
-};
-
-template <class Body>
-__device__ __forceinline__ void for_each_unit(uint32_t *sched, uint32_t grab, uint64_t t0, uint64_t t1,
-                                              Body body, uint32_t drain = 0) {
-  if (!sched) {
-    for (uint64_t t = t0 + blockIdx.x; t < t1; t += gridDim.x) {
-      body(t, NoHook());
-      drain_stores(drain);
-    }
-    return;
-  }
-  // a ticket k covers units [t0 + k*grab, t0 + (k+1)*grab)
-  __shared__ uint32_t s_next[2];
-  if (threadIdx.x == 0)
-    s_next[0] = __hip_atomic_fetch_add(&sched[0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  __syncthreads();
-  uint64_t t = t0 + (uint64_t)s_next[0] * grab;
-  int slot = 1;
-  while (t < t1) {
-    // the next ticket is grabbed before this one's loads; its value is
-    // published after the last unit's last add and before that unit's stores
-    // (the body's hook), where every load has been waited for, so the wait
-    // costs little (a wait with stores pending is vmcnt(0))
-    uint32_t nxt;  // meaningful in lane 0 only; no merge value, so no wait at the branch join
-    if (threadIdx.x == 0)
-      nxt = __hip_atomic_fetch_add(&sched[0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const uint64_t tend = (t + grab < t1) ? t + grab : t1;
-    for (uint64_t u = t; u < tend; u++) {
-      const bool last = u + 1 == tend;
-      auto publish = [&]() {
-        if (last && threadIdx.x == 0) s_next[slot] = nxt;
-      };
-      body(u, TicketHook<decltype(publish)>{publish});
-      drain_stores(drain);
-    }
-    __syncthreads();
-    t = t0 + (uint64_t)s_next[slot] * grab;
-    slot ^= 1;
-  }
-  if (threadIdx.x == 0) {
-    // every ticket grab of this workgroup precedes its done increment
-    const uint32_t prev = __hip_atomic_fetch_add(&sched[1], 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-    if (prev == gridDim.x - 1) {  // last workgroup: no grab is outstanding
-      __hip_atomic_store(&sched[0], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(&sched[1], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
-}
-
-// Tile order: unit t of a launch of n units runs tile tile_order(t).  With
-// 2^L segments the order interleaves them -- consecutive units (the ones in
-// flight together across the chip) spread over 2^L equal stretches of every
-// input instead of one contiguous window -- a bijection on [0, n) for any n
-// (segment s holds q + (s < r) tiles, q = n >> L, r = n mod 2^L; the last r
-// units are the long segments' extra tiles).  L = 0: linear.
-__device__ __forceinline__ uint64_t tile_order(uint64_t t, uint64_t n, uint32_t L) {
-  if (!L) return t;
-  const uint64_t S = 1ull << L, q = n >> L, r = n & (S - 1);
-  uint64_t seg, idx;
-  if (t < (q << L)) {
-    seg = t & (S - 1);
-    idx = t >> L;
-  } else {
-    seg = t - (q << L);
-    idx = q;
-  }
-  return seg * q + (seg < r ? seg : r) + idx;
-}
-
-// ------------------------------------------------------------ kernels ------
-
-template <class Op, int BLOCK, int U, int POL, int ENG>
-__global__ __launch_bounds__(BLOCK) void k_reduce_single(SingleArgs a) {
-  const int tid = threadIdx.x;
-  uint32_t voff[U];
-#pragma unroll
-  for (int u = 0; u < U; u++) voff[u] = (uint32_t)((u * BLOCK + tid) * kPacket);
-  ArgInputs raw{a.in};
-  if (blockIdx.x == 0) scalar_part<Op>(a.out, raw, a.n, a.head, a.npkt, a.tail, tid);
-  if (a.npkt == 0) return;  // (the host never passes a sched counter then)
-  const uint64_t shift = (uint64_t)a.head * Op::kEsz;
-  Shifted<ArgInputs> in{raw, shift};
-  char *outb = a.out + shift;
-  constexpr uint64_t TILE = (uint64_t)BLOCK * U;
-  for_each_unit(a.sched, a.grab, 0, a.ntiles, [&](uint64_t u, auto hook) {
-    const uint64_t t = tile_order(u, a.ntiles, a.order);
-    const uint64_t pkt0 = t * TILE;
-    const uint64_t left = a.npkt - pkt0;
-    const uint32_t tile_bytes = (uint32_t)((left < TILE ? left : TILE) * kPacket);
-    // the dynamic schedule's tiles pace their load burst (group_at)
-    unit_body<Op, U, POL, ENG, decltype(hook)::kDynamic>(outb, in, a.n, pkt0 * kPacket, tile_bytes, voff, hook);
-  }, a.drain);
-}
-
-// The plan's device pointer table is read through the constant address space
-// (4): the loads are then scalar (s_load) and the pointers known uniform.
-// Through a generic pointer the compiler emits a flat load -- whose
-// s_waitcnt vmcnt(0) drains every buffer load in flight -- and a
-// readfirstlane waterfall loop around every buffer load using the pointer.
-typedef const char *const __attribute__((address_space(4))) ConstPtr;
-
-struct TableInputs {
-  const char *const *p;
-  __device__ const char *operator()(int k) const { return ((ConstPtr *)p)[k]; }
-};
-
-typedef const PlanDesc __attribute__((address_space(4))) ConstDesc;
-typedef const uint32_t __attribute__((address_space(4))) ConstU32;
-
-__device__ __forceinline__ PlanDesc load_desc(const PlanDesc *desc, uint32_t c) {
-  const ConstDesc *q = (const ConstDesc *)desc + c;  // scalar loads
-  PlanDesc d;
-  d.out = q->out;
-  d.npkt = q->npkt;
-  d.tile_begin = q->tile_begin;
-  d.n = q->n;
-  d.head = q->head;
-  d.tail = q->tail;
-  d.pad = 0;
-  return d;
-}
-
-// All computes of a plan in one launch.  Global unit t belongs to compute
-// unit_comp[t] (the host's table: one scalar load, instead of a search over
-// the computes' first units whose dependent probes cost several
-// microseconds in the first unit of every workgroup of a small plan).
-template <class Op, int BLOCK, int U, int POL, int ENG>
-__global__ __launch_bounds__(BLOCK) void k_reduce_plan(PlanArgs a) {
-  const int tid = threadIdx.x;
-  uint32_t voff[U];
-#pragma unroll
-  for (int u = 0; u < U; u++) voff[u] = (uint32_t)((u * BLOCK + tid) * kPacket);
-  constexpr uint64_t TILE = (uint64_t)BLOCK * U;
-  for_each_unit(a.sched, a.grab, a.t_begin, a.t_end, [&](uint64_t t, auto hook) {
-    const uint32_t c = a.unit_comp ? ((ConstU32 *)a.unit_comp)[t] : 0u;
-    const PlanDesc d = load_desc(a.desc, c);
-    const uint64_t lt = t - d.tile_begin;
-    TableInputs raw{a.ptrs + (uint64_t)c * a.stride};
-    if (lt == 0) scalar_part<Op, POL>(d.out, raw, d.n, d.head, d.npkt, d.tail, tid);
-    const uint64_t pkt0 = lt * TILE;
-    if (pkt0 >= d.npkt) {  // a scalar-only compute: nothing to load or store
-      hook();
-      return;
-    }
-    const uint64_t shift = (uint64_t)d.head * Op::kEsz;
-    Shifted<TableInputs> in{raw, shift};
-    const uint64_t left = d.npkt - pkt0;
-    const uint32_t tile_bytes = (uint32_t)((left < TILE ? left : TILE) * kPacket);
-    unit_body<Op, U, POL, ENG>(d.out + shift, in, d.n, pkt0 * kPacket, tile_bytes, voff, hook);
-  });
-}
 
 // ------------------------------------------------------- synthetic inputs --
 
@@ -822,369 +148,6 @@ __global__ __launch_bounds__(64) void k_counter_add(uint32_t *ctr, uint32_t v) {
   if (threadIdx.x == 0) __hip_atomic_fetch_add(ctr, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// ------------------------------------------------------------ step programs --
-//
-// A stream-ordered pipeline step is a short ordered list: ready-token phases,
-// the transport's batched copies, done-token phases, the step's reductions,
-// the fused transfers' done tokens.  Launched one by one that is a
-// k_sigwait_phases before every copy or reduction kernel.  A PROGRAM folds
-// the signal/wait phases that precede a batch of units into that batch's
-// kernel as a PROLOGUE: workgroup 0's first wave runs the phases in order
-// (system-scope release stores of the epochs, bounded acquire spins -- as
-// k_sigwait_phases), then publishes the launch's sequence number in the
-// program's gate word; every other workgroup waits for that word before its
-// first unit.  The units are the tiles of the batch's computes (reductions in
-// the program's type, or exact byte copies), statically interleaved over the
-// grid like the plan kernel.
-//
-// Measured alternative (round 3, profiles/r03f_progstep_*.jsonl): running a
-// whole step -- several unit batches with completion gates between them --
-// in one launch.  Completions then need grid-wide counting (atomics on one
-// line from every workgroup) and, MI355X's L2 being per XCD, a system-scope
-// L2 writeback per workgroup before each count and an invalidate after each
-// gate: 40-170 us per step against 18-22 us for the separate launches.  A
-// kernel boundary does that cache maintenance once per XCD.  So units that
-// depend on other units stay in separate launches; only the token phases
-// move into the kernels.
-//
-// Coherence of the prologue: no unit of the launch touches its data before
-// the gate opens, so the data the phases waited for (peers' writes over
-// xGMI) is read after it arrived, as it is by a kernel launched after a
-// separate k_sigwait_phases; the launch's own stores are released at its
-// end like any kernel's.
-
-constexpr int kProgPol = kDefPol;  // nt loads, nt stores (the library's default policy)
-
-// Phases [0, count) on one wave (lanes = flags), as k_sigwait_phases.
-//
-// `light` (opt-in, HICCL_PROG_FENCES=light): relaxed system-scope token stores
-// and no fence after the waits.  A program's tokens never publish data of
-// their own launch -- a done token follows the copies or reductions of an
-// EARLIER launch (complete, and released, at that kernel's end; a peer's
-// buffer written through with the peer policy), a ready token only says a
-// buffer an earlier launch read is free -- and this launch's units start
-// after the gate, on workgroups whose L1 holds none of their data (the
-// kernel-start acquire invalidated it and nothing read it since).  The wave
-// issues a phase's stores only after its polls of the previous phase have
-// returned (the loop exits on the loaded value).  Fenced mode (the
-// default: release stores, an acquire fence per phase after relaxed polls, a
-// release gate store) orders workgroup 0 after the peers by the memory model,
-// and the other workgroups after workgroup 0 by an agent-scope acquire after
-// their gate polls (k_program); light mode leaves the gate hand-off relaxed.
-__device__ __forceinline__ void prog_phases(const ProgArgs &a, uint32_t count, uint32_t lane, uint32_t add) {
-  for (uint32_t p = 0; p < count; p++) {
-    const ConstU32 *q = (const ConstU32 *)&a.phase[p];
-    const uint32_t s0 = q[0], s1 = q[1], w0 = q[2], w1 = q[3];
-    const uint32_t epoch = a.epoch[p] + add;
-    for (uint32_t i = s0 + lane; i < s1; i += 64) {
-      uint32_t *f = ((uint32_t *const __attribute__((address_space(4))) *)a.sig)[i];
-      if (a.light)
-        __hip_atomic_store(f, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      else
-        __hip_atomic_store(f, epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-    for (uint32_t i = w0 + lane; i < w1; i += 64) {
-      const uint32_t *f = ((const uint32_t *const __attribute__((address_space(4))) *)a.wait)[i];
-      const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
-      // relaxed polls (no cache invalidate per poll); the fence below acquires
-      while ((int32_t)(__hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) - epoch) < 0) {
-        __builtin_amdgcn_s_sleep(2);
-        if (a.err && __hip_atomic_load(a.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)) break;
-        if (__builtin_amdgcn_s_memrealtime() - t0 > a.timeout_ticks) {
-          if (a.err) __hip_atomic_store(a.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-          break;
-        }
-      }
-    }
-    // fenced mode: each lane's acquire half of its polls, after its last
-    // poll; then every lane's waits (and acquires) precede any store of the
-    // next phase -- a wave-level barrier whose wavefront-scope fences carry
-    // the ordering from lane to lane (only this wave runs the phases, so no
-    // workgroup barrier is available here)
-    if (!a.light) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  }
-}
-
-// Bounded wait of one lane until the gate word holds this launch's `seq`;
-// on a time-out or an error recorded by anyone it gives up (the grid drains,
-// the host reports the error).  Relaxed polls with backoff: hundreds of
-// workgroups poll one line.  Equality, not >=: the word holds the previous
-// launch's value until workgroup 0 stores ours, and no two launches of a
-// program share a value (64-bit, hiccl_program_launch), so a later eager
-// launch's value can never open a replay's gate early.
-__device__ __forceinline__ void prog_gate_wait(const ProgArgs &a, uint64_t seq) {
-  const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
-  uint32_t nap = 1;
-  while (__hip_atomic_load(a.gate, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != seq) {
-    for (uint32_t i = 0; i < nap; i++) __builtin_amdgcn_s_sleep(2);
-    if (nap < 8) nap <<= 1;
-    if (a.err && __hip_atomic_load(a.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)) return;
-    if (__builtin_amdgcn_s_memrealtime() - t0 > a.timeout_ticks) {
-      if (a.err) __hip_atomic_store(a.err, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      return;
-    }
-  }
-}
-
-template <class Op, int U, int POL>
-__device__ __forceinline__ void prog_unit_of(const PlanDesc &d, TableInputs raw, uint64_t lt, int tid,
-                                             const uint32_t (&voff)[U]) {
-  constexpr uint64_t TILE = (uint64_t)kProgBlock * U;
-  if (lt == 0) scalar_part<Op, POL>(d.out, raw, d.n, d.head, d.npkt, d.tail, tid);
-  const uint64_t pkt0 = lt * TILE;
-  if (pkt0 >= d.npkt) return;
-  const uint64_t shift = (uint64_t)d.head * Op::kEsz;
-  Shifted<TableInputs> in{raw, shift};
-  const uint64_t left = d.npkt - pkt0;
-  const uint32_t tile_bytes = (uint32_t)((left < TILE ? left : TILE) * kPacket);
-  unit_body<Op, U, POL, kTile>(d.out + shift, in, d.n, pkt0 * kPacket, tile_bytes, voff);
-}
-
-// A unit under its compute's peer policy (the plan's hiccl_reduce_plan_set_peer
-// flags, kept in the descriptor: bit 0 stores, bit 1 loads; workgroup-uniform).
-template <class Op, int U>
-__device__ __forceinline__ void prog_unit_peer(uint32_t peer, const PlanDesc &d, TableInputs raw, uint64_t lt,
-                                               int tid, const uint32_t (&voff)[U]) {
-  constexpr int L = kProgPol % 10, S = kProgPol / 10;
-  switch (peer & 3u) {
-    case 0: prog_unit_of<Op, U, kProgPol>(d, raw, lt, tid, voff); break;
-    case 1: prog_unit_of<Op, U, 10 * kPolStoreSys + L>(d, raw, lt, tid, voff); break;
-    case 2: prog_unit_of<Op, U, 10 * S + kPolLoadSys>(d, raw, lt, tid, voff); break;
-    default: prog_unit_of<Op, U, 10 * kPolStoreSys + kPolLoadSys>(d, raw, lt, tid, voff); break;
-  }
-}
-
-template <class Op, int U>
-__global__ __launch_bounds__(kProgBlock) void k_program(ProgArgs a) {
-  const int tid = threadIdx.x;
-  uint32_t voff[U];
-#pragma unroll
-  for (int u = 0; u < U; u++) voff[u] = (uint32_t)((u * kProgBlock + tid) * kPacket);
-  if (a.nphase) {
-    const uint32_t add = a.epoch_dev ? __hip_atomic_load(a.epoch_dev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
-    const uint64_t seq = a.seq + add;
-    if (blockIdx.x == 0) {
-      if (tid < 64) {
-        prog_phases(a, a.nphase, (uint32_t)tid, add);
-        if (tid == 0) {
-          if (a.light)
-            __hip_atomic_store(a.gate, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          else
-            __hip_atomic_store(a.gate, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-        }
-      }
-    } else if (tid == 0) {
-      prog_gate_wait(a, seq);
-      // Fenced mode: an agent-scope acquire closes the relaxed gate polls,
-      // pairing with workgroup 0's agent-scope release store of the gate,
-      // which follows workgroup 0's system-scope acquire of the peers'
-      // tokens.  That orders this workgroup after the tokens for writes made
-      // on THIS GPU.  It is not a guarantee for a peer GPU's writes: on a
-      // part with several XCDs workgroup 0's system-scope acquire
-      // invalidates only its own XCD's L2, and an agent-scope acquire on
-      // another XCD does not drop non-coherent L2 lines there.  Peer data
-      // stays visible because no L2 holds a line of it (peer puts store
-      // write-through, HICCL_PEER_STORES; fused reads load system-scope,
-      // HICCL_PEER_LOADS; and the kernel-start invalidate) -- the same
-      // cache argument `light` rests on, and unconfirmed until a run with
-      // one GPU per rank.  Agent scope, not system: a system-scope acquire
-      // per workgroup (1,024 L2 invalidations per launch) cost ~8 us per
-      // C5 step (profiles/r04f_progstep.jsonl).  The workgroup barrier
-      // below carries it to the other lanes.
-      if (!a.light) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    }
-    __syncthreads();
-  }
-  for (uint64_t t = blockIdx.x; t < a.nunits; t += gridDim.x) {
-    const uint32_t c = a.unit_comp ? ((ConstU32 *)a.unit_comp)[t] : 0u;
-    const ConstDesc *q = (const ConstDesc *)a.desc + c;
-    const PlanDesc d = load_desc(a.desc, c);
-    const uint32_t flags = q->pad;  // bit 0: exact byte copy; bits 1-2: peer stores / peer loads
-    TableInputs raw{a.ptrs + (uint64_t)c * a.stride};
-    if (flags & 1u)
-      prog_unit_peer<OpRaw, U>(flags >> 1, d, raw, t - d.tile_begin, tid, voff);
-    else
-      prog_unit_peer<Op, U>(flags >> 1, d, raw, t - d.tile_begin, tid, voff);
-  }
-}
-
-// ------------------------------------------------------- kernel tables ----
-
-// The one list of element types: (dtype, acc) -> (element op, tuned).  The
-// headline types (f32, bf16 and f16 with the native accumulator) are TUNED: they get
-// the full tuning table, the others every engine's default shape.  Every
-// per-dtype lookup below goes through it.
-template <int DT, class O, bool TUNED>
-struct Elem {
-  static constexpr int dtype = DT;
-  typedef O Op;
-  static constexpr bool tuned = TUNED;
-};
-
-template <class R, class F>
-R with_elem(int dtype, int acc, R unknown, F f) {
-  switch (dtype) {
-    case HICCL_FLOAT32: return f(Elem<HICCL_FLOAT32, OpF32, true>());
-    case HICCL_BFLOAT16:
-      return acc == HICCL_ACC_WIDE ? f(Elem<HICCL_BFLOAT16, OpBF16Wide, false>())
-                                   : f(Elem<HICCL_BFLOAT16, OpBF16, true>());
-    case HICCL_FLOAT16:
-      return acc == HICCL_ACC_WIDE ? f(Elem<HICCL_FLOAT16, OpF16Wide, false>())
-                                   : f(Elem<HICCL_FLOAT16, OpF16, true>());
-    case HICCL_FLOAT64: return f(Elem<HICCL_FLOAT64, OpF64, false>());
-    case HICCL_UINT64: return f(Elem<HICCL_UINT64, OpU64, false>());
-    case HICCL_INT32: return f(Elem<HICCL_INT32, OpI32, false>());
-    case HICCL_BYTES: return f(Elem<HICCL_BYTES, OpRaw, false>());
-    default: return unknown;
-  }
-}
-
-// P of the phased engine: 16 packets per lane (acc + two in-flight loads =
-// 3 x 64 VGPRs at 512 lanes) unless the accumulator is wider than a packet
-// (bf16 / f16 wide: f32x8) or the compiler reassociates the adds and holds more
-// registers (int32: exact, so it may) -- then 8.
-template <class Op>
-constexpr int phase_p_of() {
-  return (sizeof(typename Op::acc_t) > 16 || std::is_same<Op, OpI32>::value) ? 8 : 16;
-}
-
-// ---- single-compute dispatch (template instantiation table)
-
-template <class Op, int B, int U, int POL, int ENG = kTile>
-void launch_single_t(SingleArgs a, dim3 grid, hipStream_t s) {
-  hipLaunchKernelGGL((k_reduce_single<Op, B, U, POL, ENG>), grid, dim3(B), 0, s, a);
-}
-
-template <class Op, int B, int U>
-single_fn pick_nt(int pol) {
-  switch (pol) {
-    case 0: return launch_single_t<Op, B, U, 0>;
-    case 1: return launch_single_t<Op, B, U, 1>;
-    case 10: return launch_single_t<Op, B, U, 10>;
-    case 11: return launch_single_t<Op, B, U, 11>;
-    case 20: return launch_single_t<Op, B, U, 20>;
-    case 21: return launch_single_t<Op, B, U, 21>;
-    case 10 * kPolStoreSys + 1: return launch_single_t<Op, B, U, 10 * kPolStoreSys + 1>;
-    default: return nullptr;
-  }
-}
-
-template <class Op, int B>
-single_fn pick_u(int u, int pol) {
-  switch (u) {
-    case 1: return pick_nt<Op, B, 1>(pol);
-    case 2: return pick_nt<Op, B, 2>(pol);
-    case 4: return pick_nt<Op, B, 4>(pol);
-    // wide tiles for few inputs (32 packets per lane in flight at n = 4 / 2)
-    case 8: return pol == kDefPol && B == 256 ? launch_single_t<Op, B, 8, kDefPol> : nullptr;
-    case 16: return pol == kDefPol && B == 256 ? launch_single_t<Op, B, 16, kDefPol> : nullptr;
-    default: return nullptr;
-  }
-}
-
-// Phased engine: the default shape for every type; the headline types also
-// get the sweep shapes (chunk 64-128 KiB) and cache-policy variants.
-template <class Op, bool TUNED>
-single_fn pick_phase(int block, int unroll, int pol) {
-  constexpr int PD = phase_p_of<Op>();
-  if (block == kPhBlock && unroll == PD) {
-    switch (pol) {
-      case 11: return launch_single_t<Op, kPhBlock, PD, 11, kPhase>;
-      case 10 * kPolStoreSys + 1: return launch_single_t<Op, kPhBlock, PD, 10 * kPolStoreSys + 1, kPhase>;
-      case 1: if constexpr (TUNED) return launch_single_t<Op, kPhBlock, PD, 1, kPhase>; break;
-      case 10: if constexpr (TUNED) return launch_single_t<Op, kPhBlock, PD, 10, kPhase>; break;
-      case 21: if constexpr (TUNED) return launch_single_t<Op, kPhBlock, PD, 21, kPhase>; break;
-      case 0: if constexpr (TUNED) return launch_single_t<Op, kPhBlock, PD, 0, kPhase>; break;
-      default: break;
-    }
-    return nullptr;
-  }
-  if constexpr (TUNED) {
-    if (pol != kDefPol) return nullptr;
-    if (block == 1024 && unroll == 4) return launch_single_t<Op, 1024, 4, 11, kPhase>;
-    if constexpr (PD == 16) {
-      if (block == 512 && unroll == 8) return launch_single_t<Op, 512, 8, 11, kPhase>;
-      if (block == 1024 && unroll == 8) return launch_single_t<Op, 1024, 8, 11, kPhase>;
-      if (block == 256 && unroll == 16) return launch_single_t<Op, 256, 16, 11, kPhase>;
-    } else {
-      if (block == 512 && unroll == 4) return launch_single_t<Op, 512, 4, 11, kPhase>;
-    }
-  }
-  return nullptr;
-}
-
-// Full tuning table for the headline types; default shape for the rest.
-template <class Op, bool TUNED>
-single_fn pick_single_op(int engine, int block, int unroll, int pol) {
-  if (engine == HICCL_ENGINE_PHASE) return pick_phase<Op, TUNED>(block, unroll, pol);
-  if constexpr (TUNED) {
-    if (block == 256) return pick_u<Op, 256>(unroll, pol);
-    if (block == 512) return pick_u<Op, 512>(unroll, pol);
-    return nullptr;
-  } else {
-    if (block != kDefBlock || unroll != kDefUnroll) return nullptr;
-    if (pol == 10 * kPolStoreSys + 1) return launch_single_t<Op, kDefBlock, kDefUnroll, 10 * kPolStoreSys + 1>;
-    return pol == kDefPol ? launch_single_t<Op, kDefBlock, kDefUnroll, kDefPol> : nullptr;
-  }
-}
-
-// ---- plan dispatch
-//
-// Plan kernels (and one-shot calls with > 64 inputs, which run as a
-// one-compute plan) come in the PHASE engine's default shape and the TILE
-// engine at 256 lanes x U packets, U = 4 for every type and also 1 or 2 for
-// the headline types (f32, bf16 / f16 native).  Cache policy: nt loads and stores.
-
-template <class Op, int ENG, int U, int POL = kDefPol>
-void launch_plan_t(const PlanArgs &a, dim3 grid, hipStream_t s) {
-  constexpr int B = ENG == kPhase ? kPhBlock : kDefBlock;
-  hipLaunchKernelGGL((k_reduce_plan<Op, B, U, POL, ENG>), grid, dim3(B), 0, s, a);
-}
-
-// The plan kernels' cache policy: nt loads and stores, or a plan's peer
-// policy (hiccl_reduce_plan_set_peer: system-scope stores and/or loads) --
-// those in the PHASE engine's default shape and TILE at U = 4 (and 2 for the
-// headline types: a pipeline step's small batches).
-template <class Op, bool TUNED, int POL>
-plan_fn pick_plan_pol(int engine, int unroll) {
-  constexpr bool DEF = POL == kDefPol;
-  if (engine == HICCL_ENGINE_PHASE) return launch_plan_t<Op, kPhase, phase_p_of<Op>(), POL>;
-  switch (unroll) {
-    case 0:
-    case 4: return launch_plan_t<Op, kTile, 4, POL>;
-    case 2: if constexpr (TUNED) return launch_plan_t<Op, kTile, 2, POL>; break;
-    case 8: if constexpr (TUNED && DEF) return launch_plan_t<Op, kTile, 8>; break;
-    case 16: if constexpr (TUNED && DEF) return launch_plan_t<Op, kTile, 16>; break;
-    case 1: if constexpr (TUNED && DEF) return launch_plan_t<Op, kTile, 1>; break;
-    default: break;
-  }
-  return nullptr;
-}
-
-template <class Op, bool TUNED>
-plan_fn pick_plan_eng(int engine, int unroll, int pol) {
-  constexpr int L = kDefPol % 10, S = kDefPol / 10;
-  switch (pol) {
-    case kDefPol: return pick_plan_pol<Op, TUNED, kDefPol>(engine, unroll);
-    case 10 * kPolStoreSys + L: return pick_plan_pol<Op, TUNED, 10 * kPolStoreSys + L>(engine, unroll);
-    case 10 * S + kPolLoadSys: return pick_plan_pol<Op, TUNED, 10 * S + kPolLoadSys>(engine, unroll);
-    case 10 * kPolStoreSys + kPolLoadSys:
-      return pick_plan_pol<Op, TUNED, 10 * kPolStoreSys + kPolLoadSys>(engine, unroll);
-    default: return nullptr;
-  }
-}
-
-// ---- program dispatch: TILE at 256 lanes x 4 packets, the headline types
-// also x 2 (a pipeline step's small batches)
-
-template <class Op, int U>
-void launch_prog_t(const ProgArgs &a, dim3 grid, hipStream_t s) {
-  hipLaunchKernelGGL((k_program<Op, U>), grid, dim3(kProgBlock), 0, s, a);
-}
-
 }  // namespace
 
 // ---------------------------------------------- what kernels.h declares ----
@@ -1192,40 +155,32 @@ void launch_prog_t(const ProgArgs &a, dim3 grid, hipStream_t s) {
 namespace hiccl_impl {
 
 size_t esize(int dtype) {
-  return with_elem(dtype, HICCL_ACC_NATIVE, (size_t)0, [](auto e) { return (size_t)decltype(e)::Op::kEsz; });
+  return with_elem_sum(dtype, HICCL_ACC_NATIVE, (size_t)0, [](auto e) { return (size_t)decltype(e)::Op::kEsz; });
 }
 
-bool tuned_type(int dtype, int acc) {
-  return with_elem(dtype, acc, false, [](auto e) { return decltype(e)::tuned; });
+bool tuned_type(int dtype, int acc, int op) {
+  // no MAX / MIN op is tuned (engine.h's list), so the other half is not asked
+  return part_tuned<kPartSum>(dtype, acc, op);
 }
 
 int phase_p(int dtype, int acc) {
-  return with_elem(dtype, acc, 16, [](auto e) { return phase_p_of<typename decltype(e)::Op>(); });
+  return with_elem_sum(dtype, acc, 16, [](auto e) { return phase_p_of<typename decltype(e)::Op>(); });
 }
 
-single_fn pick_single(int dtype, int acc, int engine, int block, int unroll, int pol) {
-  return with_elem(dtype, acc, (single_fn) nullptr, [&](auto e) {
-    typedef decltype(e) E;
-    return pick_single_op<typename E::Op, E::tuned>(engine, block, unroll, pol);
-  });
+// SUM's kernels are this unit's; MAX and MIN come from reduce_ops.hip.
+single_fn pick_single(int dtype, int acc, int op, int engine, int block, int unroll, int pol) {
+  if (op != HICCL_OP_SUM) return pick_single_maxmin(dtype, acc, op, engine, block, unroll, pol);
+  return part_single<kPartSum>(dtype, acc, op, engine, block, unroll, pol);
 }
 
-plan_fn pick_plan(int dtype, int acc, int engine, int unroll, int pol) {
-  return with_elem(dtype, acc, (plan_fn) nullptr, [&](auto e) {
-    typedef decltype(e) E;
-    return pick_plan_eng<typename E::Op, E::tuned>(engine, unroll, pol);
-  });
+plan_fn pick_plan(int dtype, int acc, int op, int engine, int unroll, int pol) {
+  if (op != HICCL_OP_SUM) return pick_plan_maxmin(dtype, acc, op, engine, unroll, pol);
+  return part_plan<kPartSum>(dtype, acc, op, engine, unroll, pol);
 }
 
-prog_fn pick_prog(int dtype, int unroll) {
-  // programs accumulate natively only (hiccl_program_add_plan)
-  return with_elem(dtype, HICCL_ACC_NATIVE, (prog_fn) nullptr, [&](auto e) -> prog_fn {
-    typedef decltype(e) E;
-    if constexpr (sizeof(typename E::Op::acc_t) > kPacket) return nullptr;  // the f32-accumulating ops
-    else if (unroll != 2) return launch_prog_t<typename E::Op, 4>;
-    else if constexpr (E::tuned) return launch_prog_t<typename E::Op, 2>;
-    else return nullptr;
-  });
+prog_fn pick_prog(int dtype, int op, int unroll) {
+  if (op != HICCL_OP_SUM) return pick_prog_maxmin(dtype, op, unroll);
+  return part_prog<kPartSum>(dtype, op, unroll);
 }
 
 void launch_sigwait_phases(const SigPhaseArgs &a, hipStream_t s) {
@@ -1237,7 +192,7 @@ void launch_counter_add(uint32_t *ctr, uint32_t v, hipStream_t s) {
 }
 
 bool launch_fill(int dtype, unsigned blocks, hipStream_t s, char *out, uint64_t count, uint64_t key, uint64_t first) {
-  return with_elem(dtype, HICCL_ACC_NATIVE, false, [&](auto e) {
+  return with_elem_sum(dtype, HICCL_ACC_NATIVE, false, [&](auto e) {
     typedef decltype(e) E;
     // the floating types: f32, f64, bf16, f16
     if constexpr (std::is_floating_point<typename E::Op::sacc_t>::value ||

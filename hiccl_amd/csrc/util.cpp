@@ -2,7 +2,7 @@
 // facts, synthetic inputs, stream copies, bucket allocations.
 #include "runtime.h"
 
-#define HICCL_VERSION_INT 200  // 0.2.0 (0.2: HICCL_FLOAT16)
+#define HICCL_VERSION_INT 300  // 0.3.0 (0.2: HICCL_FLOAT16; 0.3: hiccl_op_t, MAX and MIN)
 
 using namespace hiccl_impl;
 

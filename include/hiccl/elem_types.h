@@ -1,0 +1,111 @@
+// include/hiccl/elem_types.h -- the 2-byte element types of Comm<T> /
+// Compute<T>: HiCCL::bf16 and HiCCL::f16 (storage structs whose `+=` is the
+// reference's `T acc = 0; acc += x` in that type).  Plain C++, no dependency:
+// compute.h and ops.h include it, and so can a host-only test.
+#ifndef HICCL_ELEM_TYPES_H
+#define HICCL_ELEM_TYPES_H
+
+#include <cstdint>
+#include <cstring>
+
+namespace HiCCL {
+
+// bfloat16 storage type for Comm<bf16> / Compute<bf16>.  The arithmetic is
+// the reference's `T acc = 0; acc += x` (compute.h:7-9) with T = bf16: an
+// f32 add rounded to nearest-even bf16 after every add -- the host port
+// below and the GPU kernels (HICCL_BFLOAT16, HICCL_ACC_NATIVE) give the same
+// bits.  Two 2-byte types have a reduction: this one (HICCL_BFLOAT16) and
+// f16 below (HICCL_FLOAT16, with the compiler's _Float16 where it has one);
+// other 2-byte types (int16_t, uint16_t) fail to compile.
+struct bf16 {
+  uint16_t bits = 0;
+  bf16() = default;
+  bf16(int v) : bits(round((float)v)) {}  // T acc = 0
+  explicit bf16(float f) : bits(round(f)) {}
+  explicit operator float() const {
+    uint32_t w = (uint32_t)bits << 16;
+    float f;
+    std::memcpy(&f, &w, 4);
+    return f;
+  }
+  bf16 &operator+=(bf16 o) {
+    bits = round((float)*this + (float)o);
+    return *this;
+  }
+  bool operator==(bf16 o) const { return bits == o.bits; }
+  bool operator!=(bf16 o) const { return bits != o.bits; }
+  static uint16_t round(float f) {  // round to nearest even; NaN stays NaN
+    uint32_t w;
+    std::memcpy(&w, &f, 4);
+    if ((w & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((w >> 16) | 0x40);
+    w += 0x7fffu + ((w >> 16) & 1u);
+    return (uint16_t)(w >> 16);
+  }
+};
+static_assert(sizeof(bf16) == 2, "bf16 storage");
+
+// IEEE half (binary16) storage type for Comm<f16> / Compute<f16>, shaped
+// like bf16 above.  `+=` widens both operands (exact), adds in f32 and rounds
+// to nearest-even half: the same bits as a half add, since f32's 24
+// significand bits >= 2 * 11 + 2 make the double rounding innocuous.  The host
+// port below and the GPU kernels (HICCL_FLOAT16, HICCL_ACC_NATIVE: a native
+// v_pk_add_f16) give the same bits; a NaN stays a NaN (payloads may differ).
+struct f16 {
+  uint16_t bits = 0;
+  f16() = default;
+  f16(int v) : bits(round((float)v)) {}  // T acc = 0
+  explicit f16(float f) : bits(round(f)) {}
+  explicit operator float() const {
+    const uint32_t sign = (uint32_t)(bits & 0x8000u) << 16;
+    uint32_t e = (bits >> 10) & 0x1fu, m = bits & 0x3ffu, w;
+    if (e == 0x1fu) {
+      w = sign | 0x7f800000u | (m << 13);  // Inf / NaN
+    } else if (e) {
+      w = sign | ((e + 112u) << 23) | (m << 13);
+    } else if (m) {  // subnormal: m * 2^-24, normalised
+      e = 113;
+      while (!(m & 0x400u)) {
+        m <<= 1;
+        e--;
+      }
+      w = sign | (e << 23) | ((m & 0x3ffu) << 13);
+    } else {
+      w = sign;
+    }
+    float f;
+    std::memcpy(&f, &w, 4);
+    return f;
+  }
+  f16 &operator+=(f16 o) {
+    bits = round((float)*this + (float)o);
+    return *this;
+  }
+  bool operator==(f16 o) const { return bits == o.bits; }
+  bool operator!=(f16 o) const { return bits != o.bits; }
+  // round to nearest even; overflow gives Inf, results below 2^-14 are
+  // subnormal halves, NaN stays NaN
+  static uint16_t round(float f) {
+    uint32_t w;
+    std::memcpy(&w, &f, 4);
+    const uint16_t sign = (uint16_t)((w >> 16) & 0x8000u);
+    const uint32_t a = w & 0x7fffffffu;
+    if (a > 0x7f800000u) return (uint16_t)(sign | 0x7e00u | ((a >> 13) & 0x3ffu));  // NaN (quiet)
+    if (a >= 0x47800000u) return (uint16_t)(sign | 0x7c00u);  // >= 2^16 (Inf too): Inf
+    if (a >= 0x38800000u) {  // normal half (>= 2^-14); a carry out of the mantissa moves into the
+                             // exponent, and from 65520 on into Inf
+      const uint32_t r = a - 0x38000000u + 0xfffu + ((a >> 13) & 1u);
+      return (uint16_t)(sign | (r >> 13));
+    }
+    if (a < 0x33000000u) return sign;  // < 2^-25: rounds to zero (2^-25 itself ties to even, zero)
+    // subnormal half: the 24-bit significand shifted down to units of 2^-24
+    const uint32_t e = a >> 23, sig = (a & 0x7fffffu) | 0x800000u;
+    const uint32_t shift = 126u - e;  // 14..24
+    const uint32_t q = sig >> shift, rem = sig & ((1u << shift) - 1u), half = 1u << (shift - 1);
+    return (uint16_t)(sign | (q + ((rem > half || (rem == half && (q & 1u))) ? 1u : 0u)));
+  }
+};
+static_assert(sizeof(f16) == 2, "f16 storage");
+
+}  // namespace HiCCL
+
+#endif  // HICCL_ELEM_TYPES_H

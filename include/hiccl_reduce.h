@@ -51,6 +51,29 @@ typedef enum {
   HICCL_ACC_WIDE = 1    /* accumulate bf16 / f16 in f32, round once: NOT reference-bitwise */
 } hiccl_acc_t;
 
+/* Reduction operator: out[i] = fold(op, identity, in[0][i], ..., in[n-1][i]),
+ * folded in list order from the identity -- the reference's loop with T a
+ * type whose T(0) is the identity and whose += is the op (include/hiccl/ops.h:
+ * HiCCL::maxof<U>, HiCCL::minof<U>).
+ *   SUM  the default; every entry without an `op` argument sums.
+ *   MAX, MIN on f32, f64, bf16, f16: IEEE 754-2019 maximum / minimum.  Any
+ *        NaN input gives a NaN output, -0 < +0, subnormals are kept, nothing
+ *        is rounded (a bf16 max is exact).  Identity -Inf (MAX) / +Inf (MIN):
+ *        n == 0 writes it, and all -0 inputs give -0 under MAX.
+ *        HICCL_INT32: signed compare, identities INT32_MIN / INT32_MAX.
+ *        HICCL_UINT64: unsigned compare, identities 0 / UINT64_MAX.
+ * HICCL_BYTES (a copy) and HICCL_ACC_WIDE (a rounding mode of sums) take SUM
+ * only: another op with either is refused with hipErrorInvalidValue.
+ * MAX and MIN run every engine's default shape (TILE 256 x 4, PHASE's default
+ * chunk; nt or system-scope write-through stores; the plans' peer policies;
+ * programs at 4 packets): they have no tuning table, and AUTO treats them as
+ * it treats f64.  (Values left free so that a product can follow.) */
+typedef enum {
+  HICCL_OP_SUM = 0,
+  HICCL_OP_MAX = 1,
+  HICCL_OP_MIN = 2
+} hiccl_op_t;
+
 /* Kernel engine (both compute the same bits; they differ in access order).
  *   TILE   all n inputs of a 16 KiB-per-input tile are loaded together.
  *   PHASE  a workgroup sweeps a 128 KiB chunk of input 0, then of input 1,
@@ -163,6 +186,11 @@ typedef struct {
 
 int hiccl_reduce_ex(int dtype, void *out, const void *const *in, int n, size_t count,
                     void *stream, const hiccl_reduce_config_t *cfg);
+/* hiccl_reduce_ex under operator `op` (hiccl_op_t; HICCL_OP_SUM: the same
+ * call).  cfg NULL = defaults, as hiccl_reduce; n > 64 inputs run on the plan
+ * kernel as there.  n == 0 writes the operator's identity. */
+int hiccl_reduce_op(int dtype, int op, void *out, const void *const *in, int n, size_t count,
+                    void *stream, const hiccl_reduce_config_t *cfg);
 
 /* What AUTO (engine, TILE unroll / PHASE packets per lane, workgroups per
  * CU, dynamic unit schedule 1/0) picks for a one-shot call of n inputs of
@@ -181,6 +209,10 @@ int hiccl_reduce_auto_choice(int dtype, int acc, size_t count, double n, int cus
  * with TILE unroll 2 / 4 or AUTO resolves the same way (tests pin the GPU
  * tier's AUTO expectations to this answer on the host). */
 int hiccl_reduce_auto_choice_ex(int dtype, const hiccl_reduce_config_t *cfg, size_t count, double n, int cus,
+                                int *engine, int *unroll, int *blocks_per_cu, int *dynamic, int *store_policy);
+/* The same for hiccl_reduce_op.  No threshold has been measured for MAX or
+ * MIN: they follow the dtype's rules with the tuned shapes left out. */
+int hiccl_reduce_auto_choice_op(int dtype, int op, const hiccl_reduce_config_t *cfg, size_t count, double n, int cus,
                                 int *engine, int *unroll, int *blocks_per_cu, int *dynamic, int *store_policy);
 
 /* ----------------------------------------------------------------------
@@ -221,6 +253,13 @@ typedef struct hiccl_reduce_plan hiccl_reduce_plan_t;
 
 int hiccl_reduce_plan_create(hiccl_reduce_plan_t **plan, int dtype, int device);
 int hiccl_reduce_plan_set_acc(hiccl_reduce_plan_t *plan, int acc);
+/* The plan's operator (hiccl_op_t; default HICCL_OP_SUM).  May be called at
+ * any time, like set_acc: the next launch re-uploads, and launch_each honours
+ * it.  Refused for a HICCL_BYTES plan and while the plan's acc is
+ * HICCL_ACC_WIDE (and set_acc / set_config refuse WIDE under MAX / MIN).
+ * hiccl_reduce_plan_op: the operator, -1 for NULL. */
+int hiccl_reduce_plan_set_op(hiccl_reduce_plan_t *plan, int op);
+int hiccl_reduce_plan_op(const hiccl_reduce_plan_t *plan);
 /* Engine for the plan's launches (hiccl_engine_t; default AUTO, decided from
  * the total packets of all computes at the first launch after an add). */
 int hiccl_reduce_plan_set_engine(hiccl_reduce_plan_t *plan, int engine);
@@ -324,6 +363,9 @@ int hiccl_host_pipe_create(hiccl_host_pipe_t **pipe, int dtype, int device, size
                            int depth);
 int hiccl_host_pipe_reduce(hiccl_host_pipe_t *pipe, void *out, const void *const *in, int n,
                            size_t count);
+/* The operator of the pipe's later reductions (hiccl_op_t; default SUM);
+ * refused for a HICCL_BYTES pipe. */
+int hiccl_host_pipe_set_op(hiccl_host_pipe_t *pipe, int op);
 void hiccl_host_pipe_destroy(hiccl_host_pipe_t *pipe);
 
 /* ----------------------------------------------------------------------
@@ -389,7 +431,9 @@ int hiccl_signal_wait_phases(const hiccl_signal_phase_t *phases, int nphases, co
  *   is supplied per launch.
  * add_plan appends the plan's computes as of this call (later adds to the
  *   plan are not seen); the plan's dtype must be the program's or
- *   HICCL_BYTES; native accumulation only.  Computes of several plans form
+ *   HICCL_BYTES; native accumulation only.  The program takes the operator
+ *   of the first reducing plan added; a later reducing plan with another
+ *   operator is refused (HICCL_BYTES plans join any program).  Computes of several plans form
  *   one batch: they must not depend on each other.  Each plan's store form
  *   carries over as the plan decided it (hiccl_reduce_plan_store_policy, by
  *   that plan's own size): a program joining several plans may write more

@@ -1,0 +1,127 @@
+#!/usr/bin/env python3
+"""MAX against SUM on the flagship shape, in alternating fresh processes.
+
+    python tools/ops_ab.py --alternate 5 --out profiles/r09a_ops_ab.jsonl
+    python tools/ops_ab.py --leg max            (one leg, one JSON line)
+
+The shape is config 2's: n = 8 inputs of 2^28 f32 in the bucket layout
+(hiccl_amd.bucket), under AUTO.  The two legs are
+
+    sum   hiccl_reduce, the kernel every earlier measurement timed
+    max   hiccl_reduce_op with HICCL_OP_MAX (untuned: AUTO's answer for it is
+          recorded in the line)
+
+Each leg runs in a process of its own (a child started by --alternate, under a
+time limit; the parent process never opens the GPU): fill the inputs with
+fill_uniform, `warmup` launches, then `steps` launches each between two
+device events.  The line holds the median, minimum and maximum kernel time,
+the bandwidth at the median ((n + 1) x count x 4 bytes) and a sample check:
+4,096 seeded elements of the output against the in-order sum / the maximum of
+the same elements of the inputs (uniform [-1, 1): no NaN, no zero of either
+sign, so NumPy's maximum states the expected word).  DESIGN.md section 5, M18.
+"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def run_leg(a):
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import hiccl_amd
+    from hiccl_amd import _lib as L
+
+    op = {"sum": L.HICCL_OP_SUM, "max": L.HICCL_OP_MAX, "min": L.HICCL_OP_MIN}[a.leg]
+    count = 1 << a.log2count
+    dev = "cuda:0"
+    ins, out = hiccl_amd.bucket(a.n, count, dtype=torch.float32, device=dev)
+    for k, t in enumerate(ins):
+        hiccl_amd.fill_uniform(t, 1234, k)
+    torch.cuda.synchronize()
+
+    def launch():
+        hiccl_amd.reduce(out, ins, op=op)  # SUM: hiccl_reduce itself
+
+    for _ in range(a.warmup):
+        launch()
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(a.steps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        launch()
+        e1.record()
+        e1.synchronize()
+        times.append(e0.elapsed_time(e1))
+    times.sort()
+    idx = torch.from_numpy(np.random.default_rng(7).integers(0, count, 4096)).to(dev)
+    got = out[idx].cpu().numpy()
+    rows = np.stack([t[idx].cpu().numpy() for t in ins])
+    if a.leg == "sum":
+        exp = np.zeros(len(got), np.float32)
+        for r in rows:
+            exp = (exp + r).astype(np.float32)
+    else:
+        exp = rows.max(axis=0) if a.leg == "max" else rows.min(axis=0)
+    med = times[len(times) // 2]
+    line = {"probe": "ops_ab", "leg": a.leg, "round": a.round, "n": a.n, "count": count, "layout": "bucket",
+            "warmup": a.warmup, "steps": a.steps, "median_ms": round(med, 5), "min_ms": round(times[0], 5),
+            "max_ms": round(times[-1], 5), "tbps_median": round((a.n + 1) * count * 4 / med / 1e9, 4),
+            "auto": hiccl_amd.auto_choice(torch.float32, count, a.n, op=op,
+                                          cus=torch.cuda.get_device_properties(0).multi_processor_count),
+            "sample_ok": bool(np.array_equal(got.view(np.uint32), exp.view(np.uint32))),
+            "device": torch.cuda.get_device_name(0)}
+    print(json.dumps(line), flush=True)
+
+
+def alternate(a):
+    lines = []
+    for r in range(1, a.alternate + 1):
+        for leg in ("max", "sum"):
+            cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--leg", leg,
+                   "--round", str(r), "--n", str(a.n), "--log2count", str(a.log2count), "--steps", str(a.steps),
+                   "--warmup", str(a.warmup)]
+            p = subprocess.run(cmd, capture_output=True, text=True)
+            if p.returncode != 0:  # a leg that failed or ran out of time ends the run: nothing more is started
+                sys.stderr.write(p.stdout + p.stderr)
+                sys.exit(f"ops_ab: leg {leg} round {r} ended with status {p.returncode}")
+            line = p.stdout.strip().splitlines()[-1]
+            json.loads(line)
+            lines.append(line)
+            print(line, flush=True)
+            if a.out:
+                with open(a.out, "a") as fh:
+                    fh.write(line + "\n")
+    med = lambda leg: sorted(json.loads(ln)["median_ms"] for ln in lines if json.loads(ln)["leg"] == leg)  # noqa: E731
+    for leg in ("max", "sum"):
+        v = med(leg)
+        print(f"# {leg}: median of medians {v[len(v) // 2]:.4f} ms, range {v[0]:.4f}-{v[-1]:.4f}", flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--leg", choices=["sum", "max", "min"])
+    ap.add_argument("--alternate", type=int, default=0, help="rounds of (max, sum), each leg in a fresh process")
+    ap.add_argument("--out", help="append the lines to this file")
+    ap.add_argument("--round", type=int, default=1)
+    ap.add_argument("--n", type=int, default=8)
+    ap.add_argument("--log2count", type=int, default=28)
+    ap.add_argument("--steps", type=int, default=40)
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--limit", type=int, default=120, help="seconds a leg may take")
+    a = ap.parse_args()
+    if a.alternate:
+        alternate(a)
+    elif a.leg:
+        run_leg(a)
+    else:
+        ap.error("give --leg or --alternate")
+
+
+if __name__ == "__main__":
+    main()
