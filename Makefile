@@ -14,10 +14,12 @@ all: $(LIB) $(PROBE) cpp oracle
 $(PROBE): tools/hbm_probe.hip
 	$(HIPCC) $(HIPFLAGS) -o $@ $<
 
-# The library: two kernel translation units over one header of templates
-# (engine.h) -- reduce.hip, the SUM kernels, and reduce_ops.hip, the MAX / MIN
-# kernels, minutes each and compiled side by side -- and the host files
-# (seconds each), as objects under build/obj, linked once.
+# The library: three kernel translation units over one header of templates
+# (engine.h) -- reduce.hip, the SUM kernels, reduce_ops.hip, the MAX / MIN
+# kernels, and reduce_prod.hip, the PROD and bitwise kernels, compiled side by
+# side (reduce.hip the longest) -- and the host files (seconds each), as
+# objects under build/obj, linked once.  The link order is the order of the
+# library's code objects: the SUM unit first, new units last.
 # Both are compiled by hipcc's clang at -O3 without fast-math (the AUTO rules
 # compare doubles) and without per-thread default streams; the host files as
 # plain C++, so they carry no device code.
@@ -25,7 +27,7 @@ CSRC = hiccl_amd/csrc
 OBJDIR = build/obj
 OBJFLAGS = -O3 -fPIC -std=c++17 -Wall -MMD -MP
 LIB_HOST = runtime policy oneshot plan host_pipe signal program util
-LIB_KERNELS = reduce reduce_ops
+LIB_KERNELS = reduce reduce_ops reduce_prod
 LIB_OBJS = $(LIB_KERNELS:%=$(OBJDIR)/%.o) $(LIB_HOST:%=$(OBJDIR)/%.o)
 
 # The atomic optimizer rewrites the one-lane unit-ticket grab into a
@@ -71,7 +73,8 @@ HDRS = include/hiccl.h $(wildcard include/hiccl/*.h) include/hiccl_reduce.h hicc
 CPP_BINS = build/plan_dump build/collectives_host build/collectives_host_f32 build/collectives_hip build/collectives_hip_f32 \
            build/readme_example_host build/readme_example_hip build/abi_c build/ipc_reuse build/sync_wait_probe \
            build/f16_add build/f16_compute_host build/f16_compute_hip \
-           build/ops_add build/ops_compute_host build/ops_compute_hip build/ops_comm_host build/ops_comm_hip
+           build/ops_add build/ops_compute_host build/ops_compute_hip build/ops_comm_host build/ops_comm_hip \
+           build/prod_add build/prod_compute_host build/prod_compute_hip build/prod_comm_host build/prod_comm_hip
 
 cpp: $(CPP_BINS)
 
@@ -148,6 +151,31 @@ build/ops_comm_host: tests/cpp/ops_comm.cpp $(HDRS)
 	$(CXX) $(CXXFLAGS) -fopenmp -DHICCL_PORT_HOST -o $@ $< $(MPI_LINK)
 
 build/ops_comm_hip: tests/cpp/ops_comm.cpp $(HDRS) $(LIB)
+	@mkdir -p build
+	$(CXX) $(CXXFLAGS) $(HIP_HOST) -o $@ $< $(HIP_LINK) $(MPI_LINK)
+
+# HiCCL::prodof / bandof / borof / bxorof (include/hiccl/ops.h): `+=` against
+# the exact product rounded once (a stand-alone host program), Compute<prodof<
+# float>> / Compute<prodof<bf16>> and Comm<prodof<float>> / Comm<bxorof<
+# uint64_t>> on the host port and on the GPU (tests/test_prod_cpu.py,
+# tests/test_prod_gpu.py)
+build/prod_add: tests/cpp/prod_add.cpp $(HDRS)
+	@mkdir -p build
+	$(CXX) $(CXXFLAGS) -o $@ $<
+
+build/prod_compute_host: tests/cpp/prod_compute.cpp $(HDRS)
+	@mkdir -p build
+	$(CXX) $(CXXFLAGS) -fopenmp -DHICCL_PORT_HOST -o $@ $< $(MPI_LINK)
+
+build/prod_compute_hip: tests/cpp/prod_compute.cpp $(HDRS) $(LIB)
+	@mkdir -p build
+	$(CXX) $(CXXFLAGS) $(HIP_HOST) -o $@ $< $(HIP_LINK) $(MPI_LINK)
+
+build/prod_comm_host: tests/cpp/prod_comm.cpp $(HDRS)
+	@mkdir -p build
+	$(CXX) $(CXXFLAGS) -fopenmp -DHICCL_PORT_HOST -o $@ $< $(MPI_LINK)
+
+build/prod_comm_hip: tests/cpp/prod_comm.cpp $(HDRS) $(LIB)
 	@mkdir -p build
 	$(CXX) $(CXXFLAGS) $(HIP_HOST) -o $@ $< $(HIP_LINK) $(MPI_LINK)
 

@@ -32,6 +32,10 @@ HICCL_ACC_WIDE = 1
 HICCL_OP_SUM = 0
 HICCL_OP_MAX = 1
 HICCL_OP_MIN = 2
+HICCL_OP_PROD = 16
+HICCL_OP_BAND = 17
+HICCL_OP_BOR = 18
+HICCL_OP_BXOR = 19
 
 HICCL_ENGINE_AUTO = 0
 HICCL_ENGINE_TILE = 1

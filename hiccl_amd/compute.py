@@ -36,10 +36,14 @@ def _dtype_code(t):
 
 
 def _check_op(op, dtype):
-    """torch.int64 stands for size_t under SUM only (two's-complement adds
-    are the same bits); MAX and MIN on HICCL_UINT64 compare unsigned."""
-    if op != L.HICCL_OP_SUM and dtype == torch.int64:
+    """torch.int64 stands for size_t under the sign-agnostic operators (SUM,
+    PROD and the bitwise three: the same bits for either signedness); MAX and
+    MIN on HICCL_UINT64 compare unsigned.  The bitwise operators take the
+    integer types only."""
+    if op in (L.HICCL_OP_MAX, L.HICCL_OP_MIN) and dtype == torch.int64:
         raise TypeError("hiccl: MAX / MIN on HICCL_UINT64 compare unsigned: pass torch.uint64, not torch.int64")
+    if op in (L.HICCL_OP_BAND, L.HICCL_OP_BOR, L.HICCL_OP_BXOR) and dtype.is_floating_point:
+        raise TypeError(f"hiccl: BAND / BOR / BXOR take the integer types only (int32, uint64), not {dtype}")
 
 
 def _check_tensor(t, what):
@@ -54,9 +58,11 @@ def _check_tensor(t, what):
 def reduce(out, inputs, count=None, stream=None, config=None, op=L.HICCL_OP_SUM):
     """out[:count] = ((0 + inputs[0]) + inputs[1]) + ... in the list order.
 
-    ``op``: HICCL_OP_SUM (default), HICCL_OP_MAX or HICCL_OP_MIN -- the same
-    fold from the operator's identity (IEEE 754-2019 maximum / minimum on the
-    floating types: a NaN input gives NaN, -0 < +0; hiccl_reduce_op).
+    ``op``: HICCL_OP_SUM (default), HICCL_OP_MAX, HICCL_OP_MIN, HICCL_OP_PROD
+    or, on the integer types, HICCL_OP_BAND / _BOR / _BXOR -- the same fold
+    from the operator's identity (IEEE 754-2019 maximum / minimum on the
+    floating types: a NaN input gives NaN, -0 < +0; PROD: one multiply per
+    input, rounded to the type, integers wrap; hiccl_reduce_op).
 
     Mirrors one compute of compute.h: inputs are summed in list order with
     the accumulator starting at 0 in the element type.  ``out`` may be one
@@ -194,7 +200,8 @@ class Compute:
 
     def set_op(self, op):
         """Operator of the plan's launches (hiccl_reduce_plan_set_op:
-        HICCL_OP_SUM / _MAX / _MIN), at any time; the next launch re-uploads."""
+        HICCL_OP_SUM / _MAX / _MIN / _PROD / _BAND / _BOR / _BXOR), at any
+        time; the next launch re-uploads."""
         _check_op(op, self.dtype)
         L.check(L.lib().hiccl_reduce_plan_set_op(self._plan, op), "plan_set_op")
 

@@ -2,9 +2,10 @@
 // shares: the element ops, the TILE and PHASE engines, the unit schedules, the
 // one-shot / plan / program kernels and their instantiation tables.
 //
-// The library's kernels are compiled as two translation units that run side
+// The library's kernels are compiled as three translation units that run side
 // by side in the build: reduce.hip instantiates the tables for the SUM ops
-// (kPartSum) and reduce_ops.hip for the MAX / MIN ops (kPartMaxMin).  Both
+// (kPartSum), reduce_ops.hip for the MAX / MIN ops (kPartMaxMin) and
+// reduce_prod.hip for PROD and the bitwise ops (kPartProd).  All
 // take their ops from the one list below (with_elem<PART>), so a type or an
 // operator is still added in one place.  Everything here is in an anonymous
 // namespace: a kernel belongs to the unit that instantiates it.
@@ -133,6 +134,7 @@ struct OpU64 {
 
 struct OpI32 {  // two's-complement wrap-around, done in unsigned
   static constexpr bool kWidens = false;
+  static constexpr bool kHalfChunk = true;  // phase_p_of
   static constexpr int kEsz = 4;
   typedef u32x4 acc_t;
   __device__ static acc_t zero() { return (u32x4)(0u); }
@@ -367,6 +369,7 @@ struct OpBF16MM {
 template <bool MAX, class T, class VT>
 struct OpIntMM {
   static constexpr bool kWidens = false;
+  static constexpr bool kHalfChunk = sizeof(T) == 4;  // phase_p_of
   static constexpr int kEsz = sizeof(T);
   static constexpr T kId = MAX ? std::numeric_limits<T>::min() : std::numeric_limits<T>::max();
   typedef VT acc_t;
@@ -384,6 +387,102 @@ template <bool MAX> using OpF64MM = OpFloatMM<MAX, double, f64x2>;
 template <bool MAX> using OpF16MM = OpFloatMM<MAX, half_t, f16x8>;
 template <bool MAX> using OpI32MM = OpIntMM<MAX, int32_t, i32x4>;
 template <bool MAX> using OpU64MM = OpIntMM<MAX, uint64_t, u64x2>;
+
+// -------------------------------------------------- PROD and bitwise ops --
+// PROD: zero() is 1 and add() one multiply, rounded to T (nearest even,
+// subnormals kept) -- the second arithmetic under the parity contract: one
+// rounding per step, strictly in list order.  There are only multiplies, so
+// nothing can fuse, and a floating multiply is not re-associable, so the
+// floating ops need no kPinAcc.  1 * x is x for every x but a signalling NaN
+// (NaNs compare by NaN-ness), so the compiler may drop the first multiply.
+
+// f32, f64, f16: the packet is a vector of T and so is the accumulator (f16:
+// one v_pk_mul_f16 per two elements, no conversion).
+template <class T, class VT>
+struct OpFloatProd {
+  static constexpr bool kWidens = false;
+  static constexpr int kEsz = sizeof(T);
+  typedef VT acc_t;
+  __device__ static acc_t zero() { return (VT)((T)1.0f); }
+  __device__ static acc_t add(acc_t a, u32x4 p) { return a * __builtin_bit_cast(VT, p); }
+  __device__ static u32x4 pack(acc_t a) { return __builtin_bit_cast(u32x4, a); }
+  typedef T sacc_t;
+  __device__ static sacc_t szero() { return (T)1.0f; }
+  __device__ static sacc_t sadd(sacc_t a, const char *p) { return a * gld<T>(p); }
+  __device__ static void sstore(char *p, sacc_t a) { gst<T>(p, a); }
+};
+
+// bf16: OpBF16's shape with a multiply in place of the add -- widen both
+// halves (exact), multiply in f32, round to nearest even back to bf16 after
+// EVERY multiply, the accumulator kept packed.  The f32 product of two bf16
+// values is exact (16 significand bits) except below 2^-134, half of bf16's
+// smallest subnormal, where f32's own subnormals run out of bits: there the
+// f32 rounding gives at most 2^-134 and the bf16 rounding (a tie at most, to
+// even) gives zero, as one rounding of the exact product does.
+struct OpBF16Prod {
+  static constexpr bool kWidens = true;
+  static constexpr int kEsz = 2;
+  static constexpr uint32_t kOne = 0x3f803f80u;  // 1.0 | 1.0
+  typedef u32x4 acc_t;
+  __device__ static acc_t zero() { return (u32x4)(kOne); }
+  // not an inline constant: from a scalar register, as OpBF16MM's
+  __device__ static acc_t tile_zero() {
+    uint32_t k;
+    asm("s_mov_b32 %0, %1" : "=s"(k) : "i"(kOne));
+    return (u32x4)(k);
+  }
+  __device__ static acc_t add(acc_t a, u32x4 p) {
+    acc_t r;
+#pragma unroll
+    for (int w = 0; w < 4; w++)
+      r[w] = bf_pack_opaque(bf_lo(a[w]) * bf_lo(p[w]), bf_hi(a[w]) * bf_hi(p[w]));
+    return r;
+  }
+  __device__ static u32x4 pack(acc_t a) { return a; }
+  typedef float sacc_t;  // a widened bf16
+  __device__ static sacc_t szero() { return 1.0f; }
+  __device__ static sacc_t sadd(sacc_t a, const char *p) {
+    float s = a * __uint_as_float((uint32_t)(gld<uint16_t>(p)) << 16);
+    return __uint_as_float((uint32_t)bf_round(s) << 16);
+  }
+  __device__ static void sstore(char *p, sacc_t a) { gst<uint16_t>(p, bf_round(a)); }
+};
+
+// int32 and uint64, PROD and the three bitwise operators: wrap-around
+// multiply (the low bits, the same for either signedness) and AND / OR / XOR,
+// all done in unsigned.  Exact, so re-associable across inputs: kPinAcc.
+constexpr int kIntProd = 0, kIntAnd = 1, kIntOr = 2, kIntXor = 3;
+
+template <int OP, class V>
+__device__ __forceinline__ V int_fold(V a, V b) {  // unsigned, scalar or vector
+  if constexpr (OP == kIntProd) return a * b;
+  else if constexpr (OP == kIntAnd) return a & b;
+  else if constexpr (OP == kIntOr) return a | b;
+  else return a ^ b;
+}
+
+template <int OP, class T, class VT>
+struct OpIntFold {
+  static constexpr bool kWidens = false;
+  static constexpr bool kPinAcc = true;
+  static constexpr bool kHalfChunk = sizeof(T) == 4;  // phase_p_of
+  static constexpr int kEsz = sizeof(T);
+  static constexpr T kId = OP == kIntProd ? (T)1 : OP == kIntAnd ? (T)~(T)0 : (T)0;
+  typedef VT acc_t;
+  __device__ static acc_t zero() { return (VT)(kId); }
+  __device__ static acc_t add(acc_t a, u32x4 p) { return int_fold<OP>(a, __builtin_bit_cast(VT, p)); }
+  __device__ static u32x4 pack(acc_t a) { return __builtin_bit_cast(u32x4, a); }
+  typedef T sacc_t;
+  __device__ static sacc_t szero() { return kId; }
+  __device__ static sacc_t sadd(sacc_t a, const char *p) { return int_fold<OP>(a, gld<T>(p)); }
+  __device__ static void sstore(char *p, sacc_t a) { gst<T>(p, a); }
+};
+
+typedef OpFloatProd<float, f32x4> OpF32Prod;
+typedef OpFloatProd<double, f64x2> OpF64Prod;
+typedef OpFloatProd<half_t, f16x8> OpF16Prod;
+template <int OP> using OpI32Fold = OpIntFold<OP, uint32_t, u32x4>;
+template <int OP> using OpU64Fold = OpIntFold<OP, uint64_t, u64x2>;
 
 // ----------------------------------------------------------- tile engine --
 //
@@ -1024,10 +1123,10 @@ __global__ __launch_bounds__(kProgBlock) void k_program(ProgArgs a) {
 
 // The one list of element types: (dtype, acc, op) -> (element op, tuned).  The
 // headline types (f32, bf16 and f16 with the native accumulator) under SUM are
-// TUNED: they get the full tuning table, the others -- every MAX / MIN op
-// among them -- every engine's default shape.  Every per-dtype lookup below
-// goes through it.  PART names the half of the list a translation unit
-// instantiates (engine.h's head): a key of the other half answers `unknown`.
+// TUNED: they get the full tuning table, the others -- every MAX / MIN, PROD
+// and bitwise op among them -- every engine's default shape.  Every per-dtype
+// lookup below goes through it.  PART names the part of the list a translation
+// unit instantiates (engine.h's head): a key of another part answers `unknown`.
 template <int DT, class O, bool TUNED>
 struct Elem {
   static constexpr int dtype = DT;
@@ -1037,6 +1136,7 @@ struct Elem {
 
 constexpr int kPartSum = 0;
 constexpr int kPartMaxMin = 1;
+constexpr int kPartProd = 2;  // PROD, BAND, BOR, BXOR
 
 // MAX and MIN of the six arithmetic types; HICCL_BYTES has no operator.
 template <bool MAX, class R, class F>
@@ -1070,9 +1170,42 @@ R with_elem_sum(int dtype, int acc, R unknown, F f) {
   }
 }
 
+// PROD of the six arithmetic types.
+template <class R, class F>
+R with_elem_prod(int dtype, R unknown, F f) {
+  switch (dtype) {
+    case HICCL_FLOAT32: return f(Elem<HICCL_FLOAT32, OpF32Prod, false>());
+    case HICCL_BFLOAT16: return f(Elem<HICCL_BFLOAT16, OpBF16Prod, false>());
+    case HICCL_FLOAT16: return f(Elem<HICCL_FLOAT16, OpF16Prod, false>());
+    case HICCL_FLOAT64: return f(Elem<HICCL_FLOAT64, OpF64Prod, false>());
+    case HICCL_UINT64: return f(Elem<HICCL_UINT64, OpU64Fold<kIntProd>, false>());
+    case HICCL_INT32: return f(Elem<HICCL_INT32, OpI32Fold<kIntProd>, false>());
+    default: return unknown;
+  }
+}
+
+// BAND / BOR / BXOR: the two integer types only.
+template <int OP, class R, class F>
+R with_elem_bit(int dtype, R unknown, F f) {
+  switch (dtype) {
+    case HICCL_UINT64: return f(Elem<HICCL_UINT64, OpU64Fold<OP>, false>());
+    case HICCL_INT32: return f(Elem<HICCL_INT32, OpI32Fold<OP>, false>());
+    default: return unknown;
+  }
+}
+
 template <int PART, class R, class F>
 R with_elem(int dtype, int acc, int op, R unknown, F f) {
-  if constexpr (PART == kPartMaxMin) {
+  if constexpr (PART == kPartProd) {
+    if (acc != HICCL_ACC_NATIVE) return unknown;
+    switch (op) {
+      case HICCL_OP_PROD: return with_elem_prod(dtype, unknown, f);
+      case HICCL_OP_BAND: return with_elem_bit<kIntAnd>(dtype, unknown, f);
+      case HICCL_OP_BOR: return with_elem_bit<kIntOr>(dtype, unknown, f);
+      case HICCL_OP_BXOR: return with_elem_bit<kIntXor>(dtype, unknown, f);
+      default: return unknown;
+    }
+  } else if constexpr (PART == kPartMaxMin) {
     // the f32 accumulator of HICCL_ACC_WIDE belongs to SUM alone
     if (acc != HICCL_ACC_NATIVE) return unknown;
     if (op == HICCL_OP_MAX) return with_elem_mm<true>(dtype, unknown, f);
@@ -1090,11 +1223,15 @@ R with_elem(int dtype, int acc, int op, R unknown, F f) {
 // registers (int32: exact, so it may) -- then 8.  The chunk is a property of
 // (dtype, acc): int32 takes 8 under every operator, so the host sizes a plan's
 // units without asking for the operator.
+// An int32 op says so itself (kHalfChunk).
+template <class Op, class = void>
+struct half_chunk : std::false_type {};
+template <class Op>
+struct half_chunk<Op, std::enable_if_t<Op::kHalfChunk>> : std::true_type {};
+
 template <class Op>
 constexpr int phase_p_of() {
-  constexpr bool i32 = std::is_same<Op, OpI32>::value || std::is_same<Op, OpI32MM<true>>::value ||
-                       std::is_same<Op, OpI32MM<false>>::value;
-  return (sizeof(typename Op::acc_t) > 16 || i32) ? 8 : 16;
+  return (sizeof(typename Op::acc_t) > 16 || half_chunk<Op>::value) ? 8 : 16;
 }
 
 // ---- single-compute dispatch (template instantiation table)

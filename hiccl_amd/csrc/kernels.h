@@ -149,6 +149,10 @@ prog_fn pick_prog(int dtype, int op, int unroll);
 single_fn pick_single_maxmin(int dtype, int acc, int op, int engine, int block, int unroll, int pol);
 plan_fn pick_plan_maxmin(int dtype, int acc, int op, int engine, int unroll, int pol);
 prog_fn pick_prog_maxmin(int dtype, int op, int unroll);
+// the PROD / BAND / BOR / BXOR part (reduce_prod.hip), reached the same way
+single_fn pick_single_prod(int dtype, int acc, int op, int engine, int block, int unroll, int pol);
+plan_fn pick_plan_prod(int dtype, int acc, int op, int engine, int unroll, int pol);
+prog_fn pick_prog_prod(int dtype, int op, int unroll);
 
 // ---- the plain kernels
 

@@ -9,11 +9,12 @@
 // measured for f16; DESIGN.md section 5 (M17) records the one f16 / bf16
 // comparison.
 //
-// MAX and MIN (hiccl_op_t) are untuned under every dtype: tuned_type answers
-// false for them, so they take no wide or half-size tile and none of the
-// rules made for the tuned types; every other rule applies by dtype
-// unchanged.  No threshold below has been measured for MAX or MIN; DESIGN.md
-// section 5 (M18) records the one MAX / SUM comparison.
+// Every operator but SUM (hiccl_op_t: MAX, MIN, PROD, BAND, BOR, BXOR) is
+// untuned under every dtype: tuned_type answers false for them, so they take
+// no wide or half-size tile and none of the rules made for the tuned types;
+// every other rule applies by dtype unchanged.  No threshold below has been
+// measured for any of them; DESIGN.md section 5 records the one MAX / SUM
+// comparison (M18) and the PROD / SUM ones, f32 and uint64 (M19).
 #include "policy.h"
 
 namespace hiccl_impl {
@@ -210,13 +211,31 @@ int check_cfg(const hiccl_reduce_config_t *c, const std::string &who) {
   return 0;
 }
 
+// hiccl_op_t's values are not dense (0-2, 16-19): membership, not a range.
+bool known_op(int op) {
+  switch (op) {
+    case HICCL_OP_SUM:
+    case HICCL_OP_MAX:
+    case HICCL_OP_MIN:
+    case HICCL_OP_PROD:
+    case HICCL_OP_BAND:
+    case HICCL_OP_BOR:
+    case HICCL_OP_BXOR: return true;
+    default: return false;
+  }
+}
+
 int check_op(int dtype, int acc, int op, const std::string &who) {
-  if (op < HICCL_OP_SUM || op > HICCL_OP_MIN)
-    return fail(hipErrorInvalidValue, who + ": unknown op " + std::to_string(op));
+  if (!known_op(op)) return fail(hipErrorInvalidValue, who + ": unknown op " + std::to_string(op));
   if (op == HICCL_OP_SUM) return 0;
   if (dtype == HICCL_BYTES) return fail(hipErrorInvalidValue, who + ": HICCL_BYTES copies take HICCL_OP_SUM only");
   if (acc == HICCL_ACC_WIDE)
     return fail(hipErrorInvalidValue, who + ": HICCL_ACC_WIDE is a rounding mode of sums (HICCL_OP_SUM only)");
+  const bool bitwise = op == HICCL_OP_BAND || op == HICCL_OP_BOR || op == HICCL_OP_BXOR;
+  // an unknown dtype is left to the caller's own dtype check
+  if (bitwise && esize(dtype) && dtype != HICCL_INT32 && dtype != HICCL_UINT64)
+    return fail(hipErrorInvalidValue,
+                who + ": HICCL_OP_BAND / _BOR / _BXOR take the integer types only (HICCL_INT32, HICCL_UINT64)");
   return 0;
 }
 

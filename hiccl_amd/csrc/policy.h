@@ -25,8 +25,11 @@ Cfg resolve(const hiccl_reduce_config_t *c);
 // The enumerated and ranged fields of a caller's config (NULL: all
 // defaults), refused as `who: ...` with hipErrorInvalidValue.
 int check_cfg(const hiccl_reduce_config_t *c, const std::string &who);
-// An operator for this dtype and accumulation mode: known, and SUM for
-// HICCL_BYTES and HICCL_ACC_WIDE.  Refused as `who: ...` likewise.
+// Is `op` one of hiccl_op_t's values (which are not a range)?
+bool known_op(int op);
+// An operator for this dtype and accumulation mode: known, SUM for
+// HICCL_BYTES and HICCL_ACC_WIDE, and an integer type under the bitwise
+// operators.  Refused as `who: ...` likewise.
 int check_op(int dtype, int acc, int op, const std::string &who);
 
 // Does a launch that writes `out_bytes` from `n` inputs per output (a plan's

@@ -159,7 +159,7 @@ size_t esize(int dtype) {
 }
 
 bool tuned_type(int dtype, int acc, int op) {
-  // no MAX / MIN op is tuned (engine.h's list), so the other half is not asked
+  // no MAX / MIN, PROD or bitwise op is tuned (engine.h's list), so the other parts are not asked
   return part_tuned<kPartSum>(dtype, acc, op);
 }
 
@@ -167,18 +167,22 @@ int phase_p(int dtype, int acc) {
   return with_elem_sum(dtype, acc, 16, [](auto e) { return phase_p_of<typename decltype(e)::Op>(); });
 }
 
-// SUM's kernels are this unit's; MAX and MIN come from reduce_ops.hip.
+// SUM's kernels are this unit's; MAX and MIN come from reduce_ops.hip, PROD
+// and the bitwise operators from reduce_prod.hip.
 single_fn pick_single(int dtype, int acc, int op, int engine, int block, int unroll, int pol) {
+  if (op >= HICCL_OP_PROD) return pick_single_prod(dtype, acc, op, engine, block, unroll, pol);
   if (op != HICCL_OP_SUM) return pick_single_maxmin(dtype, acc, op, engine, block, unroll, pol);
   return part_single<kPartSum>(dtype, acc, op, engine, block, unroll, pol);
 }
 
 plan_fn pick_plan(int dtype, int acc, int op, int engine, int unroll, int pol) {
+  if (op >= HICCL_OP_PROD) return pick_plan_prod(dtype, acc, op, engine, unroll, pol);
   if (op != HICCL_OP_SUM) return pick_plan_maxmin(dtype, acc, op, engine, unroll, pol);
   return part_plan<kPartSum>(dtype, acc, op, engine, unroll, pol);
 }
 
 prog_fn pick_prog(int dtype, int op, int unroll) {
+  if (op >= HICCL_OP_PROD) return pick_prog_prod(dtype, op, unroll);
   if (op != HICCL_OP_SUM) return pick_prog_maxmin(dtype, op, unroll);
   return part_prog<kPartSum>(dtype, op, unroll);
 }

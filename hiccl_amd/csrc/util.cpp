@@ -2,7 +2,8 @@
 // facts, synthetic inputs, stream copies, bucket allocations.
 #include "runtime.h"
 
-#define HICCL_VERSION_INT 300  // 0.3.0 (0.2: HICCL_FLOAT16; 0.3: hiccl_op_t, MAX and MIN)
+// 0.4.0 (0.2: HICCL_FLOAT16; 0.3: hiccl_op_t, MAX and MIN; 0.4: PROD, BAND, BOR, BXOR)
+#define HICCL_VERSION_INT 400
 
 using namespace hiccl_impl;
 

@@ -33,10 +33,11 @@
 
 namespace HiCCL {
 
-// bf16 and f16, the 2-byte storage types: elem_types.h.  maxof<U> / minof<U>,
-// the types whose `+=` is a maximum / minimum: ops.h.
+// bf16 and f16, the 2-byte storage types: elem_types.h.  maxof<U>, minof<U>,
+// prodof<U>, bandof<U>, borof<U>, bxorof<U>, the types whose `+=` is another
+// operator: ops.h.
 
-// T -> hiccl_dtype_t (maxof<U> and minof<U>: U's; the operator is op_of<T>(), ops.h)
+// T -> hiccl_dtype_t (an operator wrapper of U: U's; the operator is op_of<T>(), ops.h)
 template <typename T>
 constexpr int dtype_of() {
   if constexpr (op_of<T>() != 0) return dtype_of<typename op_traits<T>::value_type>();
@@ -95,7 +96,7 @@ class Compute {
     static_assert(dtype_of<T>() >= 0, "HiCCL::Compute: unsupported element type");
     if (!plan) {
       check(hiccl_reduce_plan_create(&plan, dtype_of<T>(), CommBench::mydevice), "plan_create");
-      // T = maxof<U> / minof<U>: the plan runs U's MAX / MIN kernels (a step
+      // T = maxof<U> ... bxorof<U>: the plan runs U's kernels of that operator (a step
       // program takes the operator from the plan it records)
       if (op_of<T>() != HICCL_OP_SUM) check(hiccl_reduce_plan_set_op(plan, op_of<T>()), "plan_set_op");
       // HICCL_ENGINE=tile|phase|auto pins the kernel engine (same bits either

@@ -54,7 +54,7 @@ typedef enum {
 /* Reduction operator: out[i] = fold(op, identity, in[0][i], ..., in[n-1][i]),
  * folded in list order from the identity -- the reference's loop with T a
  * type whose T(0) is the identity and whose += is the op (include/hiccl/ops.h:
- * HiCCL::maxof<U>, HiCCL::minof<U>).
+ * HiCCL::maxof<U>, HiCCL::minof<U>, prodof<U>, bandof<U>, borof<U>, bxorof<U>).
  *   SUM  the default; every entry without an `op` argument sums.
  *   MAX, MIN on f32, f64, bf16, f16: IEEE 754-2019 maximum / minimum.  Any
  *        NaN input gives a NaN output, -0 < +0, subnormals are kept, nothing
@@ -62,16 +62,33 @@ typedef enum {
  *        n == 0 writes it, and all -0 inputs give -0 under MAX.
  *        HICCL_INT32: signed compare, identities INT32_MIN / INT32_MAX.
  *        HICCL_UINT64: unsigned compare, identities 0 / UINT64_MAX.
+ *   PROD on the six arithmetic types (HiCCL::prodof<U>), identity 1 (n == 0
+ *        writes 1).  f32, f64: one IEEE multiply per input, each rounded to T
+ *        (nearest even); subnormal inputs and results are kept, Inf x 0 is
+ *        NaN, the sign of a zero follows the sign rule (1 x -0 = -0); there
+ *        are only multiplies, so nothing is fused.  f16: the half multiply
+ *        itself.  bf16: widen, f32 multiply, round to nearest even to bf16
+ *        after EVERY multiply.  HICCL_INT32 / HICCL_UINT64: wrap-around
+ *        multiply (the low 32 / 64 bits, the same for either signedness).
+ *   BAND, BOR, BXOR (HiCCL::bandof / borof / bxorof) on HICCL_INT32 and
+ *        HICCL_UINT64 only, identities all-ones / 0 / 0; sign-agnostic and
+ *        exact.  On a floating dtype they are refused (hipErrorInvalidValue).
  * HICCL_BYTES (a copy) and HICCL_ACC_WIDE (a rounding mode of sums) take SUM
  * only: another op with either is refused with hipErrorInvalidValue.
- * MAX and MIN run every engine's default shape (TILE 256 x 4, PHASE's default
- * chunk; nt or system-scope write-through stores; the plans' peer policies;
- * programs at 4 packets): they have no tuning table, and AUTO treats them as
- * it treats f64.  (Values left free so that a product can follow.) */
+ * Every operator but SUM runs every engine's default shape (TILE 256 x 4,
+ * PHASE's default chunk; nt or system-scope write-through stores; the plans'
+ * peer policies; programs at 4 packets): they have no tuning table, and AUTO
+ * treats them as it treats f64.  The values are not dense: 3-15 are no
+ * operator (and stay refused as unknown), PROD and the bitwise three start
+ * at 16. */
 typedef enum {
   HICCL_OP_SUM = 0,
   HICCL_OP_MAX = 1,
-  HICCL_OP_MIN = 2
+  HICCL_OP_MIN = 2,
+  HICCL_OP_PROD = 16,
+  HICCL_OP_BAND = 17,
+  HICCL_OP_BOR = 18,
+  HICCL_OP_BXOR = 19
 } hiccl_op_t;
 
 /* Kernel engine (both compute the same bits; they differ in access order).
@@ -255,8 +272,9 @@ int hiccl_reduce_plan_create(hiccl_reduce_plan_t **plan, int dtype, int device);
 int hiccl_reduce_plan_set_acc(hiccl_reduce_plan_t *plan, int acc);
 /* The plan's operator (hiccl_op_t; default HICCL_OP_SUM).  May be called at
  * any time, like set_acc: the next launch re-uploads, and launch_each honours
- * it.  Refused for a HICCL_BYTES plan and while the plan's acc is
- * HICCL_ACC_WIDE (and set_acc / set_config refuse WIDE under MAX / MIN).
+ * it.  Refused for a HICCL_BYTES plan, while the plan's acc is
+ * HICCL_ACC_WIDE (and set_acc / set_config refuse WIDE under any operator but
+ * SUM), and for BAND / BOR / BXOR on a floating plan.
  * hiccl_reduce_plan_op: the operator, -1 for NULL. */
 int hiccl_reduce_plan_set_op(hiccl_reduce_plan_t *plan, int op);
 int hiccl_reduce_plan_op(const hiccl_reduce_plan_t *plan);
@@ -364,7 +382,7 @@ int hiccl_host_pipe_create(hiccl_host_pipe_t **pipe, int dtype, int device, size
 int hiccl_host_pipe_reduce(hiccl_host_pipe_t *pipe, void *out, const void *const *in, int n,
                            size_t count);
 /* The operator of the pipe's later reductions (hiccl_op_t; default SUM);
- * refused for a HICCL_BYTES pipe. */
+ * refused for a HICCL_BYTES pipe, and BAND / BOR / BXOR for a floating one. */
 int hiccl_host_pipe_set_op(hiccl_host_pipe_t *pipe, int op);
 void hiccl_host_pipe_destroy(hiccl_host_pipe_t *pipe);
 
