@@ -14,9 +14,10 @@ all: $(LIB) $(PROBE) cpp oracle
 $(PROBE): tools/hbm_probe.hip
 	$(HIPCC) $(HIPFLAGS) -o $@ $<
 
-# The library: three kernel translation units over one header of templates
+# The library: four kernel translation units over one header of templates
 # (engine.h) -- reduce.hip, the SUM kernels, reduce_ops.hip, the MAX / MIN
-# kernels, and reduce_prod.hip, the PROD and bitwise kernels, compiled side by
+# kernels, reduce_prod.hip, the PROD and bitwise kernels, and reduce_scale.hip,
+# the scaled sums, compiled side by
 # side (reduce.hip the longest) -- and the host files (seconds each), as
 # objects under build/obj, linked once.  The link order is the order of the
 # library's code objects: the SUM unit first, new units last.
@@ -27,7 +28,7 @@ CSRC = hiccl_amd/csrc
 OBJDIR = build/obj
 OBJFLAGS = -O3 -fPIC -std=c++17 -Wall -MMD -MP
 LIB_HOST = runtime policy oneshot plan host_pipe signal program util
-LIB_KERNELS = reduce reduce_ops reduce_prod
+LIB_KERNELS = reduce reduce_ops reduce_prod reduce_scale
 LIB_OBJS = $(LIB_KERNELS:%=$(OBJDIR)/%.o) $(LIB_HOST:%=$(OBJDIR)/%.o)
 
 # The atomic optimizer rewrites the one-lane unit-ticket grab into a
@@ -74,7 +75,8 @@ CPP_BINS = build/plan_dump build/collectives_host build/collectives_host_f32 bui
            build/readme_example_host build/readme_example_hip build/abi_c build/ipc_reuse build/sync_wait_probe \
            build/f16_add build/f16_compute_host build/f16_compute_hip \
            build/ops_add build/ops_compute_host build/ops_compute_hip build/ops_comm_host build/ops_comm_hip \
-           build/prod_add build/prod_compute_host build/prod_compute_hip build/prod_comm_host build/prod_comm_hip
+           build/prod_add build/prod_compute_host build/prod_compute_hip build/prod_comm_host build/prod_comm_hip \
+           build/scale_finish build/scale_compute_host build/scale_compute_hip
 
 cpp: $(CPP_BINS)
 
@@ -176,6 +178,22 @@ build/prod_comm_host: tests/cpp/prod_comm.cpp $(HDRS)
 	$(CXX) $(CXXFLAGS) -fopenmp -DHICCL_PORT_HOST -o $@ $< $(MPI_LINK)
 
 build/prod_comm_hip: tests/cpp/prod_comm.cpp $(HDRS) $(LIB)
+	@mkdir -p build
+	$(CXX) $(CXXFLAGS) $(HIP_HOST) -o $@ $< $(HIP_LINK) $(MPI_LINK)
+
+# Scaled sums: HiCCL::scale_finish<T> against the exact product rounded twice
+# (a stand-alone host program), Compute<float> / Compute<bf16> with set_scale
+# on the host port and on the GPU (tests/test_scale_cpu.py,
+# tests/test_scale_gpu.py)
+build/scale_finish: tests/cpp/scale_finish.cpp $(HDRS)
+	@mkdir -p build
+	$(CXX) $(CXXFLAGS) -o $@ $<
+
+build/scale_compute_host: tests/cpp/scale_compute.cpp $(HDRS)
+	@mkdir -p build
+	$(CXX) $(CXXFLAGS) -fopenmp -DHICCL_PORT_HOST -o $@ $< $(MPI_LINK)
+
+build/scale_compute_hip: tests/cpp/scale_compute.cpp $(HDRS) $(LIB)
 	@mkdir -p build
 	$(CXX) $(CXXFLAGS) $(HIP_HOST) -o $@ $< $(HIP_LINK) $(MPI_LINK)
 

@@ -7,6 +7,8 @@ argument meaning.  Both call straight into the HIP library through the C ABI
 (include/hiccl_reduce.h); device memory and streams come from torch.
 """
 import ctypes
+import math
+import numbers
 
 import torch
 
@@ -46,6 +48,28 @@ def _check_op(op, dtype):
         raise TypeError(f"hiccl: BAND / BOR / BXOR take the integer types only (int32, uint64), not {dtype}")
 
 
+def _check_scale(scale, dtype, op=L.HICCL_OP_SUM):
+    """A scaled sum (out = scale * sum, hiccl_reduce_scaled): floating types,
+    SUM, a finite scale -- refused here, before any device work.  Returns the
+    scale as a float."""
+    if isinstance(dtype, torch.dtype):
+        floating = dtype in (torch.float32, torch.float64, torch.bfloat16, torch.float16)
+    else:
+        floating = int(dtype) in (L.HICCL_FLOAT32, L.HICCL_FLOAT64, L.HICCL_BFLOAT16, L.HICCL_FLOAT16)
+    if not floating:
+        raise TypeError(f"hiccl: scaled sums take the floating types only (f32, f64, bf16, f16), not {dtype}")
+    if op != L.HICCL_OP_SUM:
+        raise ValueError("hiccl: only sums are scaled: scale= goes with HICCL_OP_SUM")
+    if isinstance(scale, torch.Tensor) and scale.ndim == 0 and not scale.is_complex():
+        scale = scale.item()  # a 0-d tensor, as 1 / torch.tensor(n)
+    if isinstance(scale, bool) or not isinstance(scale, numbers.Real):  # numpy's real scalars are Real
+        raise TypeError(f"hiccl: scale must be a real number, not {type(scale).__name__}")
+    scale = float(scale)
+    if not math.isfinite(scale):
+        raise ValueError(f"hiccl: scale must be finite, not {scale}")
+    return scale
+
+
 def _check_tensor(t, what):
     if not isinstance(t, torch.Tensor):
         raise TypeError(f"hiccl: {what} must be a torch.Tensor")
@@ -55,8 +79,13 @@ def _check_tensor(t, what):
         raise ValueError(f"hiccl: {what} must be contiguous")
 
 
-def reduce(out, inputs, count=None, stream=None, config=None, op=L.HICCL_OP_SUM):
+def reduce(out, inputs, count=None, stream=None, config=None, op=L.HICCL_OP_SUM, scale=None):
     """out[:count] = ((0 + inputs[0]) + inputs[1]) + ... in the list order.
+
+    ``scale`` (a finite number, floating dtypes, SUM only): the sum times
+    ``scale``, multiplied once at store time (hiccl_reduce_scaled) -- an
+    average is ``scale=1 / len(inputs)``.  f32 / f64: one IEEE multiply; bf16 /
+    f16: an f32 multiply rounded to f32, then rounded to the type.
 
     ``op``: HICCL_OP_SUM (default), HICCL_OP_MAX, HICCL_OP_MIN, HICCL_OP_PROD
     or, on the integer types, HICCL_OP_BAND / _BOR / _BXOR -- the same fold
@@ -88,10 +117,15 @@ def reduce(out, inputs, count=None, stream=None, config=None, op=L.HICCL_OP_SUM)
     if out.numel() < count:
         raise ValueError(f"hiccl: out has {out.numel()} < count={count} elements")
     _check_op(op, out.dtype)
+    if scale is not None:
+        scale = _check_scale(scale, out.dtype, op)
     tab = _ptr_table(ptrs)
     with torch.cuda.device(out.device):  # the library launches on the current device
         s = _stream_handle(stream, out.device)
-        if op != L.HICCL_OP_SUM:
+        if scale is not None:
+            cfg = ctypes.byref(L.ReduceConfig(**config)) if config is not None else None
+            rc = L.lib().hiccl_reduce_scaled(dt, scale, ctypes.c_void_p(out.data_ptr()), tab, len(ptrs), count, s, cfg)
+        elif op != L.HICCL_OP_SUM:
             cfg = ctypes.byref(L.ReduceConfig(**config)) if config is not None else None
             rc = L.lib().hiccl_reduce_op(dt, op, ctypes.c_void_p(out.data_ptr()), tab, len(ptrs), count, s, cfg)
         elif config is None:
@@ -104,11 +138,16 @@ def reduce(out, inputs, count=None, stream=None, config=None, op=L.HICCL_OP_SUM)
     return out
 
 
-def reduce_ptrs(dtype_code, out_ptr, in_ptrs, count, stream=None, config=None, op=L.HICCL_OP_SUM):
+def reduce_ptrs(dtype_code, out_ptr, in_ptrs, count, stream=None, config=None, op=L.HICCL_OP_SUM, scale=None):
     """Raw-pointer form (pointers already offset), used by the Comm layer."""
+    if scale is not None:
+        scale = _check_scale(scale, dtype_code, op)
     tab = _ptr_table(list(in_ptrs))
     s = _stream_handle(stream)
-    if op != L.HICCL_OP_SUM:
+    if scale is not None:
+        cfg = ctypes.byref(L.ReduceConfig(**config)) if config is not None else None
+        rc = L.lib().hiccl_reduce_scaled(dtype_code, scale, ctypes.c_void_p(out_ptr), tab, len(in_ptrs), count, s, cfg)
+    elif op != L.HICCL_OP_SUM:
         cfg = ctypes.byref(L.ReduceConfig(**config)) if config is not None else None
         rc = L.lib().hiccl_reduce_op(dtype_code, op, ctypes.c_void_p(out_ptr), tab, len(in_ptrs), count, s, cfg)
     elif config is None:
@@ -139,18 +178,22 @@ def bucket(n, count, dtype=torch.float32, device=None):
     return views[:n], views[n]
 
 
-def auto_choice(dtype, count, n, config=None, cus=256, op=L.HICCL_OP_SUM):
+def auto_choice(dtype, count, n, config=None, cus=256, op=L.HICCL_OP_SUM, scale=False):
     """What a one-shot call (and a one-compute plan at TILE unroll 2 / 4 or
     AUTO) resolves to on a GPU of ``cus`` CUs, without a device:
     ``hiccl_reduce_auto_choice_ex`` (``op`` other than SUM:
-    ``hiccl_reduce_auto_choice_op``).  ``dtype``: a torch dtype or an
+    ``hiccl_reduce_auto_choice_op``; ``scale=True``, a scaled sum:
+    ``hiccl_reduce_auto_choice_scaled``).  ``dtype``: a torch dtype or an
     HICCL_* code; ``n`` may be a plan's packet-weighted mean.  Returns a dict
     with engine, unroll, blocks_per_cu, dynamic and store_policy (2 nt, 4
     write-through); raises HicclError for a config no kernel has."""
     dt = L.DTYPE_OF_TORCH[dtype] if isinstance(dtype, torch.dtype) else int(dtype)
     cfg = ctypes.byref(L.ReduceConfig(**config)) if config else None
     out = [ctypes.c_int() for _ in range(5)]
-    if op != L.HICCL_OP_SUM:
+    if scale:
+        _check_scale(1.0, dtype if isinstance(dtype, torch.dtype) else dt, op)
+        rc = L.lib().hiccl_reduce_auto_choice_scaled(dt, cfg, count, float(n), cus, *[ctypes.byref(v) for v in out])
+    elif op != L.HICCL_OP_SUM:
         rc = L.lib().hiccl_reduce_auto_choice_op(dt, op, cfg, count, float(n), cus, *[ctypes.byref(v) for v in out])
     else:
         rc = L.lib().hiccl_reduce_auto_choice_ex(dt, cfg, count, float(n), cus, *[ctypes.byref(v) for v in out])
@@ -174,9 +217,11 @@ class Compute:
     """
 
     def __init__(self, dtype=torch.float32, device=None, myid=0, acc=L.HICCL_ACC_NATIVE,
-                 engine=L.HICCL_ENGINE_AUTO, config=None, op=L.HICCL_OP_SUM):
+                 engine=L.HICCL_ENGINE_AUTO, config=None, op=L.HICCL_OP_SUM, scale=None):
         self.dtype = dtype
         self.code = L.DTYPE_OF_TORCH[dtype]
+        if scale is not None:
+            scale = _check_scale(scale, dtype, op)
         if device is None:
             device = torch.cuda.current_device()
         self.device = device
@@ -197,6 +242,25 @@ class Compute:
             self.set_config(config)
         if op != L.HICCL_OP_SUM:
             self.set_op(op)
+        if scale is not None:
+            self.set_scale(scale)
+
+    def set_scale(self, scale):
+        """Scale of the plan's sums (hiccl_reduce_plan_set_scale): every
+        compute writes ``scale`` times its sum from the next launch on
+        (``start(each=True)`` too); ``None`` clears it.  At any time, like
+        :meth:`set_acc`.  Floating dtypes and SUM only; a program takes no
+        scaled plan."""
+        if scale is None:
+            L.check(L.lib().hiccl_reduce_plan_set_scale(self._plan, None), "plan_set_scale")
+            return
+        a = ctypes.c_double(_check_scale(scale, self.dtype, self.op()))
+        L.check(L.lib().hiccl_reduce_plan_set_scale(self._plan, ctypes.byref(a)), "plan_set_scale")
+
+    def scale(self):
+        """The plan's scale, or None (hiccl_reduce_plan_scale)."""
+        a = ctypes.c_double()
+        return a.value if L.lib().hiccl_reduce_plan_scale(self._plan, ctypes.byref(a)) == 1 else None
 
     def set_op(self, op):
         """Operator of the plan's launches (hiccl_reduce_plan_set_op:
@@ -408,11 +472,15 @@ class HostPipe:
     staging ``chunk_bytes`` per input through device memory with H2D /
     kernel / D2H pipelined over ``depth`` streams.  Blocking; same bits as
     :func:`reduce`.  Pin the tensors (``pin_memory()``) for the overlap.
-    ``op``: the operator (hiccl_host_pipe_set_op), default SUM."""
+    ``op``: the operator (hiccl_host_pipe_set_op), default SUM.  ``scale``:
+    a scaled sum (hiccl_host_pipe_set_scale), as :func:`reduce`'s."""
 
-    def __init__(self, dtype=torch.float32, device=None, chunk_bytes=0, depth=0, op=L.HICCL_OP_SUM):
+    def __init__(self, dtype=torch.float32, device=None, chunk_bytes=0, depth=0, op=L.HICCL_OP_SUM, scale=None):
         self.dtype = dtype
         self.code = L.DTYPE_OF_TORCH[dtype]
+        self._op = op
+        if scale is not None:
+            scale = _check_scale(scale, dtype, op)
         if device is None:
             device = torch.cuda.current_device()
         h = ctypes.c_void_p()
@@ -422,6 +490,16 @@ class HostPipe:
         if op != L.HICCL_OP_SUM:
             _check_op(op, dtype)
             L.check(L.lib().hiccl_host_pipe_set_op(self._pipe, op), "host_pipe_set_op")
+        if scale is not None:
+            self.set_scale(scale)
+
+    def set_scale(self, scale):
+        """Scale of the pipe's sums from the next reduce on; ``None`` clears it."""
+        if scale is None:
+            L.check(L.lib().hiccl_host_pipe_set_scale(self._pipe, None), "host_pipe_set_scale")
+            return
+        a = ctypes.c_double(_check_scale(scale, self.dtype, self._op))
+        L.check(L.lib().hiccl_host_pipe_set_scale(self._pipe, ctypes.byref(a)), "host_pipe_set_scale")
 
     def reduce(self, out, inputs, count=None):
         for k, t in enumerate([out] + list(inputs)):

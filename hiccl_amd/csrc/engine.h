@@ -2,10 +2,11 @@
 // shares: the element ops, the TILE and PHASE engines, the unit schedules, the
 // one-shot / plan / program kernels and their instantiation tables.
 //
-// The library's kernels are compiled as three translation units that run side
+// The library's kernels are compiled as four translation units that run side
 // by side in the build: reduce.hip instantiates the tables for the SUM ops
-// (kPartSum), reduce_ops.hip for the MAX / MIN ops (kPartMaxMin) and
-// reduce_prod.hip for PROD and the bitwise ops (kPartProd).  All
+// (kPartSum), reduce_ops.hip for the MAX / MIN ops (kPartMaxMin),
+// reduce_prod.hip for PROD and the bitwise ops (kPartProd) and
+// reduce_scale.hip for the post-scaled sums (kPartScale).  All
 // take their ops from the one list below (with_elem<PART>), so a type or an
 // operator is still added in one place.  Everything here is in an anonymous
 // namespace: a kernel belongs to the unit that instantiates it.
@@ -484,6 +485,116 @@ typedef OpFloatProd<half_t, f16x8> OpF16Prod;
 template <int OP> using OpI32Fold = OpIntFold<OP, uint32_t, u32x4>;
 template <int OP> using OpU64Fold = OpIntFold<OP, uint64_t, u64x2>;
 
+// ------------------------------------------------------------ scaled sums --
+// out = finish(sum, alpha): the SUM op of the same dtype and accumulator with a
+// FINISHING step at store time -- pack() and sstore() take the wave-uniform
+// alpha of the launch (Scale, kernels.h; it arrives in the kernel arguments
+// of k_reduce_single_scaled / k_reduce_plan_scaled, so it stays in SGPRs) and multiply once, after the last add.  zero() and
+// add() are the SUM op's own, so the sum is SUM's, bit for bit.
+//   f64           fl64(s * alpha)
+//   f32           fl32(s * a32), a32 = (float)alpha
+//   bf16 / f16    round_T(fl32(widen(s) * a32)): the f32 product is ROUNDED TO
+//                 F32 and then rounded to nearest even to T -- two roundings,
+//                 which is the definition (a single rounding of the exact
+//                 product differs, and so does a half multiply)
+//   ... wide      round_T(fl32(s32 * a32)), s32 the f32 accumulator
+// A multiply that follows an add cannot fuse with it.  Widen, multiply and
+// narrow stay three instructions: the product passes through an empty asm
+// (opaque_f32), so no pattern can fold the multiply into the conversion (a
+// v_fma_mixlo_f16 in place of v_mul_f32 + v_cvt_f16_f32).
+// An op without a finishing step has fin_t = NoFin (fin_of), an empty struct
+// that the engines pass along and pack_fin / sstore_fin drop: the other ops'
+// kernels do not change.
+struct NoFin {};
+
+template <class Op, class = void>
+struct fin_of {
+  typedef NoFin type;
+};
+template <class Op>
+struct fin_of<Op, std::void_t<typename Op::fin_t>> {
+  typedef typename Op::fin_t type;
+};
+template <class Op> using fin_t = typename fin_of<Op>::type;
+
+template <class Op>
+__device__ __forceinline__ u32x4 pack_fin(typename Op::acc_t a, fin_t<Op> f) {
+  if constexpr (std::is_same<fin_t<Op>, NoFin>::value) return Op::pack(a);
+  else return Op::pack(a, f);
+}
+template <class Op>
+__device__ __forceinline__ void sstore_fin(char *p, typename Op::sacc_t a, fin_t<Op> f) {
+  if constexpr (std::is_same<fin_t<Op>, NoFin>::value) Op::sstore(p, a);
+  else Op::sstore(p, a, f);
+}
+
+__device__ __forceinline__ float opaque_f32(float x) {
+  asm("" : "+v"(x));
+  return x;
+}
+// one element's finishing multiply of the 2-byte types: an f32 product,
+// rounded to f32, that the narrowing conversion cannot be merged with
+__device__ __forceinline__ float scale_f32(float s, float a32) { return opaque_f32(s * a32); }
+
+// f32, f64: one IEEE multiply of the packet by alpha.
+template <class Base, class T>
+struct OpFloatScaled : Base {
+  typedef T fin_t;
+  __device__ static T fin(const Scale &s) {
+    if constexpr (sizeof(T) == 8) return s.a64;
+    else return s.a32;
+  }
+  __device__ static u32x4 pack(typename Base::acc_t a, T alpha) { return __builtin_bit_cast(u32x4, a * alpha); }
+  __device__ static void sstore(char *p, T a, T alpha) { gst<T>(p, a * alpha); }
+};
+
+// bf16: BF16 = OpBF16 (the packed bf16 accumulator is widened, exactly) or
+// OpBF16Wide (the f32 accumulator as it is).
+template <class Base>
+struct OpBF16Scaled : Base {
+  typedef float fin_t;
+  __device__ static float fin(const Scale &s) { return s.a32; }
+  __device__ static u32x4 pack(typename Base::acc_t a, float a32) {
+    u32x4 r;
+#pragma unroll
+    for (int w = 0; w < 4; w++) {
+      if constexpr (sizeof(typename Base::acc_t) > kPacket)
+        r[w] = bf_pack(scale_f32(a[2 * w], a32), scale_f32(a[2 * w + 1], a32));
+      else
+        r[w] = bf_pack(scale_f32(bf_lo(a[w]), a32), scale_f32(bf_hi(a[w]), a32));
+    }
+    return r;
+  }
+  // the scalar accumulator of both is a float (native: a widened bf16)
+  __device__ static void sstore(char *p, float a, float a32) { gst<uint16_t>(p, bf_round(scale_f32(a, a32))); }
+};
+
+// f16: Base = OpF16 (the half accumulator is widened, exactly) or OpF16Wide.
+template <class Base>
+struct OpF16Scaled : Base {
+  typedef float fin_t;
+  __device__ static float fin(const Scale &s) { return s.a32; }
+  __device__ static u32x4 pack(typename Base::acc_t a, float a32) {
+    u32x4 r;
+#pragma unroll
+    for (int w = 0; w < 4; w++) {
+      const float lo = scale_f32((float)a[2 * w], a32), hi = scale_f32((float)a[2 * w + 1], a32);
+      r[w] = (uint32_t)f16_round(lo) | (uint32_t)f16_round(hi) << 16;
+    }
+    return r;
+  }
+  __device__ static void sstore(char *p, typename Base::sacc_t a, float a32) {
+    gst<uint16_t>(p, f16_round(scale_f32((float)a, a32)));
+  }
+};
+
+typedef OpFloatScaled<OpF32, float> OpF32Scaled;
+typedef OpFloatScaled<OpF64, double> OpF64Scaled;
+typedef OpBF16Scaled<OpBF16> OpBF16NatScaled;
+typedef OpBF16Scaled<OpBF16Wide> OpBF16WideScaled;
+typedef OpF16Scaled<OpF16> OpF16NatScaled;
+typedef OpF16Scaled<OpF16Wide> OpF16WideScaled;
+
 // ----------------------------------------------------------- tile engine --
 //
 // A compute is split as [head scalars | npkt 16-B packets | tail scalars],
@@ -505,7 +616,7 @@ struct ArgInputs {
 // and only when the compute has a head or a tail.
 template <class Op, int POL = 11, class Inputs>
 __device__ __forceinline__ void scalar_part(char *out, Inputs in, uint32_t n, uint32_t head,
-                                            uint64_t npkt, uint32_t tail, int tid) {
+                                            uint64_t npkt, uint32_t tail, int tid, fin_t<Op> fin = {}) {
   constexpr int V = kPacket / Op::kEsz;
   if (tid >= (int)(head + tail)) return;
   if constexpr (POL % 10 == kPolLoadSys) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
@@ -513,7 +624,7 @@ __device__ __forceinline__ void scalar_part(char *out, Inputs in, uint32_t n, ui
   uint64_t off = e * Op::kEsz;
   typename Op::sacc_t acc = Op::szero();
   for (uint32_t k = 0; k < n; k++) acc = Op::sadd(acc, in(k) + off);
-  Op::sstore(out + off, acc);
+  sstore_fin<Op>(out + off, acc, fin);
   if constexpr (POL / 10 == kPolStoreSys) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
 }
 
@@ -597,7 +708,7 @@ __device__ __forceinline__ typename Op::acc_t tile_zero() {
 template <class Op, int U, int POL, bool PACED = false, class Inputs, class Hook = NoHook>
 __device__ __forceinline__ void tile_body(char *outb, Inputs in, uint32_t n, uint64_t tile_off,
                                           uint32_t tile_bytes, const uint32_t (&voff)[U],
-                                          Hook before_store = Hook()) {
+                                          Hook before_store = Hook(), fin_t<Op> fin = {}) {
   typename Op::acc_t acc[U];
 #pragma unroll
   for (int u = 0; u < U; u++) acc[u] = tile_zero<Op>();
@@ -623,7 +734,7 @@ __device__ __forceinline__ void tile_body(char *outb, Inputs in, uint32_t n, uin
   }
   before_store();
 #pragma unroll
-  for (int u = 0; u < U; u++) store_pkt<POL>(w, voff[u], Op::pack(acc[u]));
+  for (int u = 0; u < U; u++) store_pkt<POL>(w, voff[u], pack_fin<Op>(acc[u], fin));
 }
 
 // Input-phased chunk (the default engine for large buckets).  A chunk =
@@ -658,7 +769,7 @@ __device__ __forceinline__ void pin_acc(typename Op::acc_t &a) {
 template <class Op, int P, int POL, class Inputs, class Hook = NoHook>
 __device__ __forceinline__ void chunk_body(char *outb, Inputs in, uint32_t n, uint64_t off,
                                            uint32_t nbytes, const uint32_t (&voff)[P],
-                                           Hook before_store = Hook()) {
+                                           Hook before_store = Hook(), fin_t<Op> fin = {}) {
   typename Op::acc_t acc[P];
 #pragma unroll
   for (int p = 0; p < P; p++) acc[p] = Op::zero();
@@ -703,7 +814,7 @@ __device__ __forceinline__ void chunk_body(char *outb, Inputs in, uint32_t n, ui
   before_store();
   rsrc_t w = make_rsrc(outb + off, nbytes);
 #pragma unroll
-  for (int p = 0; p < P; p++) store_pkt<POL>(w, voff[p], Op::pack(acc[p]));
+  for (int p = 0; p < P; p++) store_pkt<POL>(w, voff[p], pack_fin<Op>(acc[p], fin));
 }
 
 // Engines: kTile = all n inputs of a BLOCK*U tile loaded together (small
@@ -737,13 +848,14 @@ __device__ __forceinline__ uint64_t uniform64(uint64_t v) {
 // branch.
 template <class Op, int U, int POL, int ENG, bool PACED = false, class Inputs, class Hook = NoHook>
 __device__ __forceinline__ void unit_body(char *outb, Inputs in, uint32_t n, uint64_t off,
-                                          uint32_t nbytes, const uint32_t (&voff)[U], Hook hook = Hook()) {
+                                          uint32_t nbytes, const uint32_t (&voff)[U], Hook hook = Hook(),
+                                          fin_t<Op> fin = {}) {
   const uint64_t uoff = uniform64(off);
   const uint32_t ubytes = uniform32(nbytes);
   if constexpr (ENG == kPhase)
-    chunk_body<Op, U, POL>(outb, in, n, uoff, ubytes, voff, hook);
+    chunk_body<Op, U, POL>(outb, in, n, uoff, ubytes, voff, hook, fin);
   else
-    tile_body<Op, U, POL, PACED>(outb, in, n, uoff, ubytes, voff, hook);
+    tile_body<Op, U, POL, PACED>(outb, in, n, uoff, ubytes, voff, hook, fin);
 }
 
 // Body inputs shifted by the head: base(k) = in[k] + head*esz.
@@ -849,14 +961,15 @@ __device__ __forceinline__ uint64_t tile_order(uint64_t t, uint64_t n, uint32_t 
 
 // ------------------------------------------------------------ kernels ------
 
+// The one-shot kernel's body; `fin`: the scale of a scaled sum (NoFin otherwise).
 template <class Op, int BLOCK, int U, int POL, int ENG>
-__global__ __launch_bounds__(BLOCK) void k_reduce_single(SingleArgs a) {
+__device__ __forceinline__ void single_kernel(const SingleArgs &a, fin_t<Op> fin) {
   const int tid = threadIdx.x;
   uint32_t voff[U];
 #pragma unroll
   for (int u = 0; u < U; u++) voff[u] = (uint32_t)((u * BLOCK + tid) * kPacket);
   ArgInputs raw{a.in};
-  if (blockIdx.x == 0) scalar_part<Op>(a.out, raw, a.n, a.head, a.npkt, a.tail, tid);
+  if (blockIdx.x == 0) scalar_part<Op>(a.out, raw, a.n, a.head, a.npkt, a.tail, tid, fin);
   if (a.npkt == 0) return;  // (the host never passes a sched counter then)
   const uint64_t shift = (uint64_t)a.head * Op::kEsz;
   Shifted<ArgInputs> in{raw, shift};
@@ -868,8 +981,20 @@ __global__ __launch_bounds__(BLOCK) void k_reduce_single(SingleArgs a) {
     const uint64_t left = a.npkt - pkt0;
     const uint32_t tile_bytes = (uint32_t)((left < TILE ? left : TILE) * kPacket);
     // the dynamic schedule's tiles pace their load burst (group_at)
-    unit_body<Op, U, POL, ENG, decltype(hook)::kDynamic>(outb, in, a.n, pkt0 * kPacket, tile_bytes, voff, hook);
+    unit_body<Op, U, POL, ENG, decltype(hook)::kDynamic>(outb, in, a.n, pkt0 * kPacket, tile_bytes, voff, hook, fin);
   }, a.drain);
+}
+
+template <class Op, int BLOCK, int U, int POL, int ENG>
+__global__ __launch_bounds__(BLOCK) void k_reduce_single(SingleArgs a) {
+  single_kernel<Op, BLOCK, U, POL, ENG>(a, NoFin());
+}
+
+// The scaled sums' kernel: the same body with the op's alpha, which arrives in
+// the kernel arguments (scalar loads: it stays in SGPRs).
+template <class Op, int BLOCK, int U, int POL, int ENG>
+__global__ __launch_bounds__(BLOCK) void k_reduce_single_scaled(SingleArgsScaled a) {
+  single_kernel<Op, BLOCK, U, POL, ENG>(a, Op::fin(a.scale));
 }
 
 // The plan's device pointer table is read through the constant address space
@@ -927,6 +1052,38 @@ __global__ __launch_bounds__(BLOCK) void k_reduce_plan(PlanArgs a) {
     const uint64_t left = d.npkt - pkt0;
     const uint32_t tile_bytes = (uint32_t)((left < TILE ? left : TILE) * kPacket);
     unit_body<Op, U, POL, ENG>(d.out + shift, in, d.n, pkt0 * kPacket, tile_bytes, voff, hook);
+  });
+}
+
+// The scaled sums' plan kernel: k_reduce_plan (above) with the op's alpha from
+// the kernel arguments.  The two bodies are kept apart on purpose: moved into
+// one shared function, k_reduce_plan's instantiations came out with another
+// register allocation (and 3-4 instructions fewer), and the kernels of the
+// existing code objects are to stay instruction for instruction what they were.
+template <class Op, int BLOCK, int U, int POL, int ENG>
+__global__ __launch_bounds__(BLOCK) void k_reduce_plan_scaled(PlanArgsScaled a) {
+  const fin_t<Op> fin = Op::fin(a.scale);
+  const int tid = threadIdx.x;
+  uint32_t voff[U];
+#pragma unroll
+  for (int u = 0; u < U; u++) voff[u] = (uint32_t)((u * BLOCK + tid) * kPacket);
+  constexpr uint64_t TILE = (uint64_t)BLOCK * U;
+  for_each_unit(a.sched, a.grab, a.t_begin, a.t_end, [&](uint64_t t, auto hook) {
+    const uint32_t c = a.unit_comp ? ((ConstU32 *)a.unit_comp)[t] : 0u;
+    const PlanDesc d = load_desc(a.desc, c);
+    const uint64_t lt = t - d.tile_begin;
+    TableInputs raw{a.ptrs + (uint64_t)c * a.stride};
+    if (lt == 0) scalar_part<Op, POL>(d.out, raw, d.n, d.head, d.npkt, d.tail, tid, fin);
+    const uint64_t pkt0 = lt * TILE;
+    if (pkt0 >= d.npkt) {  // a scalar-only compute: nothing to load or store
+      hook();
+      return;
+    }
+    const uint64_t shift = (uint64_t)d.head * Op::kEsz;
+    Shifted<TableInputs> in{raw, shift};
+    const uint64_t left = d.npkt - pkt0;
+    const uint32_t tile_bytes = (uint32_t)((left < TILE ? left : TILE) * kPacket);
+    unit_body<Op, U, POL, ENG>(d.out + shift, in, d.n, pkt0 * kPacket, tile_bytes, voff, hook, fin);
   });
 }
 
@@ -1137,6 +1294,7 @@ struct Elem {
 constexpr int kPartSum = 0;
 constexpr int kPartMaxMin = 1;
 constexpr int kPartProd = 2;  // PROD, BAND, BOR, BXOR
+constexpr int kPartScale = 3;  // post-scaled sums (kOpScaledSum)
 
 // MAX and MIN of the six arithmetic types; HICCL_BYTES has no operator.
 template <bool MAX, class R, class F>
@@ -1194,9 +1352,27 @@ R with_elem_bit(int dtype, R unknown, F f) {
   }
 }
 
+// Scaled sums: the floating types, under either accumulator for the 2-byte
+// ones.  Untuned, like every operator but SUM.
+template <class R, class F>
+R with_elem_scale(int dtype, int acc, R unknown, F f) {
+  const bool wide = acc == HICCL_ACC_WIDE;
+  switch (dtype) {
+    case HICCL_FLOAT32: return f(Elem<HICCL_FLOAT32, OpF32Scaled, false>());
+    case HICCL_FLOAT64: return f(Elem<HICCL_FLOAT64, OpF64Scaled, false>());
+    case HICCL_BFLOAT16:
+      return wide ? f(Elem<HICCL_BFLOAT16, OpBF16WideScaled, false>()) : f(Elem<HICCL_BFLOAT16, OpBF16NatScaled, false>());
+    case HICCL_FLOAT16:
+      return wide ? f(Elem<HICCL_FLOAT16, OpF16WideScaled, false>()) : f(Elem<HICCL_FLOAT16, OpF16NatScaled, false>());
+    default: return unknown;
+  }
+}
+
 template <int PART, class R, class F>
 R with_elem(int dtype, int acc, int op, R unknown, F f) {
-  if constexpr (PART == kPartProd) {
+  if constexpr (PART == kPartScale) {
+    return op == kOpScaledSum ? with_elem_scale(dtype, acc, unknown, f) : unknown;
+  } else if constexpr (PART == kPartProd) {
     if (acc != HICCL_ACC_NATIVE) return unknown;
     switch (op) {
       case HICCL_OP_PROD: return with_elem_prod(dtype, unknown, f);
@@ -1237,8 +1413,11 @@ constexpr int phase_p_of() {
 // ---- single-compute dispatch (template instantiation table)
 
 template <class Op, int B, int U, int POL, int ENG = kTile>
-void launch_single_t(SingleArgs a, dim3 grid, hipStream_t s) {
-  hipLaunchKernelGGL((k_reduce_single<Op, B, U, POL, ENG>), grid, dim3(B), 0, s, a);
+void launch_single_t(const SingleArgsScaled &a, dim3 grid, hipStream_t s) {
+  if constexpr (std::is_same<fin_t<Op>, NoFin>::value)
+    hipLaunchKernelGGL((k_reduce_single<Op, B, U, POL, ENG>), grid, dim3(B), 0, s, (const SingleArgs &)a);
+  else
+    hipLaunchKernelGGL((k_reduce_single_scaled<Op, B, U, POL, ENG>), grid, dim3(B), 0, s, a);
 }
 
 template <class Op, int B, int U>
@@ -1322,9 +1501,12 @@ single_fn pick_single_op(int engine, int block, int unroll, int pol) {
 // the headline types (f32, bf16 / f16 native).  Cache policy: nt loads and stores.
 
 template <class Op, int ENG, int U, int POL = kDefPol>
-void launch_plan_t(const PlanArgs &a, dim3 grid, hipStream_t s) {
+void launch_plan_t(const PlanArgsScaled &a, dim3 grid, hipStream_t s) {
   constexpr int B = ENG == kPhase ? kPhBlock : kDefBlock;
-  hipLaunchKernelGGL((k_reduce_plan<Op, B, U, POL, ENG>), grid, dim3(B), 0, s, a);
+  if constexpr (std::is_same<fin_t<Op>, NoFin>::value)
+    hipLaunchKernelGGL((k_reduce_plan<Op, B, U, POL, ENG>), grid, dim3(B), 0, s, (const PlanArgs &)a);
+  else
+    hipLaunchKernelGGL((k_reduce_plan_scaled<Op, B, U, POL, ENG>), grid, dim3(B), 0, s, a);
 }
 
 // The plan kernels' cache policy: nt loads and stores, or a plan's peer

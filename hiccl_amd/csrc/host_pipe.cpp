@@ -10,6 +10,8 @@ struct hiccl_host_pipe {
   int dtype = 0;
   int device = 0;
   int op = HICCL_OP_SUM;  // hiccl_host_pipe_set_op
+  bool scaled = false;    // hiccl_host_pipe_set_scale: out = alpha * sum (op stays SUM)
+  Scale scale{0.0, 0.0f, 0u};
   size_t esz = 0;
   size_t chunk = 0;  // elements per input per chunk
   int depth = 0;
@@ -95,7 +97,9 @@ int hiccl_host_pipe_reduce(hiccl_host_pipe_t *p, void *out, const void *const *i
                       "host_pipe_reduce: H2D");
     }
     // in place into staged input 0 (exact aliasing is element-wise safe)
-    if (!err) err = hiccl_reduce_op(p->dtype, p->op, stage, dev_in.data(), n, len, s, nullptr);
+    if (!err)
+      err = reduce_call(p->dtype, p->scaled ? kOpScaledSum : p->op, p->scaled ? &p->scale : nullptr, stage,
+                        dev_in.data(), n, len, s, nullptr);
     if (!err)
       err = check_hip(hipMemcpyAsync((char *)out + lo * p->esz, stage, len * p->esz, hipMemcpyDeviceToHost, s),
                       "host_pipe_reduce: D2H");
@@ -110,7 +114,22 @@ int hiccl_host_pipe_reduce(hiccl_host_pipe_t *p, void *out, const void *const *i
 int hiccl_host_pipe_set_op(hiccl_host_pipe_t *p, int op) {
   if (!p) return fail(hipErrorInvalidValue, "host_pipe_set_op: pipe is NULL");
   if (int e = check_op(p->dtype, HICCL_ACC_NATIVE, op, "host_pipe_set_op")) return e;
+  if (p->scaled && op != HICCL_OP_SUM)
+    return fail(hipErrorInvalidValue, "host_pipe_set_op: a scaled pipe sums (HICCL_OP_SUM only): clear the scale first");
   p->op = op;
+  return 0;
+}
+
+int hiccl_host_pipe_set_scale(hiccl_host_pipe_t *p, const double *alpha) {
+  if (!p) return fail(hipErrorInvalidValue, "host_pipe_set_scale: pipe is NULL");
+  Scale sc{0.0, 0.0f, 0u};
+  if (alpha) {
+    if (int e = check_scale(p->dtype, *alpha, "host_pipe_set_scale", &sc)) return e;
+    if (p->op != HICCL_OP_SUM)
+      return fail(hipErrorInvalidValue, "host_pipe_set_scale: only sums are scaled (the pipe's op is not HICCL_OP_SUM)");
+  }
+  p->scaled = alpha != nullptr;
+  p->scale = sc;
   return 0;
 }
 

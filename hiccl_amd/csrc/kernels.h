@@ -40,6 +40,21 @@ constexpr int kPhBlock = 512;
 
 constexpr int kMaxArgInputs = 64;  // kernarg pointer table (512 B)
 
+// A scaled sum (hiccl_reduce_scaled, hiccl_reduce_plan_set_scale) travels
+// through the policy and the kernel tables as an operator of its own, which is
+// no hiccl_op_t value: the public entries never take it (known_op refuses it).
+constexpr int kOpScaledSum = 0x100;
+
+// The scale of a scaled sum: alpha as the caller gave it (f64 kernels) and
+// rounded to nearest even to f32 (every other type).  The scaled kernels take
+// it behind the arguments of the unscaled ones (SingleArgsScaled,
+// PlanArgsScaled), whose own argument structs stay as they are.
+struct Scale {
+  double a64;
+  float a32;
+  uint32_t pad;
+};
+
 struct SingleArgs {
   char *out;          // raw output pointer
   uint64_t npkt;      // body packets
@@ -52,6 +67,12 @@ struct SingleArgs {
   uint32_t grab;      // units per ticket (dynamic schedule), >= 1
   uint32_t drain;     // 1: wait for a unit's stores before the next unit's loads
   const char *in[kMaxArgInputs];
+};
+
+// What the host hands a one-shot launcher: the kernel's arguments, and the
+// scale, which only a scaled kernel (k_reduce_single_scaled) is passed.
+struct SingleArgsScaled : SingleArgs {
+  Scale scale;
 };
 
 // Descriptor of one compute in a batched plan (device memory).
@@ -76,6 +97,10 @@ struct PlanArgs {
   uint64_t t_begin, t_end;
   uint32_t *sched;  // dynamic unit counter, or NULL
   uint32_t stride, grab;
+};
+
+struct PlanArgsScaled : PlanArgs {  // as SingleArgsScaled
+  Scale scale;
 };
 
 constexpr int kMaxFlags = 64;  // signal and wait flags per launch (one per lane)
@@ -138,8 +163,8 @@ int phase_p(int dtype, int acc);    // packets per lane of the PHASE engine's de
 // ---- kernel tables: the launcher of a shape, or NULL where no kernel has it
 // (engine: HICCL_ENGINE_TILE / _PHASE; pol: 10*store + load)
 
-typedef void (*single_fn)(SingleArgs, dim3, hipStream_t);
-typedef void (*plan_fn)(const PlanArgs &, dim3, hipStream_t);
+typedef void (*single_fn)(const SingleArgsScaled &, dim3, hipStream_t);
+typedef void (*plan_fn)(const PlanArgsScaled &, dim3, hipStream_t);
 typedef void (*prog_fn)(const ProgArgs &, dim3, hipStream_t);
 
 single_fn pick_single(int dtype, int acc, int op, int engine, int block, int unroll, int pol);
@@ -153,6 +178,9 @@ prog_fn pick_prog_maxmin(int dtype, int op, int unroll);
 single_fn pick_single_prod(int dtype, int acc, int op, int engine, int block, int unroll, int pol);
 plan_fn pick_plan_prod(int dtype, int acc, int op, int engine, int unroll, int pol);
 prog_fn pick_prog_prod(int dtype, int op, int unroll);
+// the scaled sums (reduce_scale.hip; op == kOpScaledSum): no program kernels
+single_fn pick_single_scale(int dtype, int acc, int op, int engine, int block, int unroll, int pol);
+plan_fn pick_plan_scale(int dtype, int acc, int op, int engine, int unroll, int pol);
 
 // ---- the plain kernels
 

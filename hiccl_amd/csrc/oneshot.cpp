@@ -2,6 +2,8 @@
 // hiccl_reduce_auto_choice*: what AUTO would pick for it.
 #include <string.h>
 
+#include <cmath>
+
 #include "plan.h"
 
 using namespace hiccl_impl;
@@ -19,8 +21,8 @@ uint32_t log2u(int v) {
 
 // Large-n one-shot path: stage the pointer table in stream-ordered device
 // memory and run it as a one-compute plan.
-int reduce_via_table(int dtype, const Cfg &c, void *out, const void *const *in, int n, size_t count,
-                     hipStream_t s) {
+int reduce_via_table(int dtype, const Cfg &c, const Scale &scale, void *out, const void *const *in, int n,
+                     size_t count, hipStream_t s) {
   DescTable t((size_t)n, unit_pkts(c.engine, dtype, c.acc, c.unroll));
   t.add(out, in, (size_t)n, count, esize(dtype));
   const std::vector<char> host = t.image();
@@ -33,11 +35,12 @@ int reduce_via_table(int dtype, const Cfg &c, void *out, const void *const *in, 
     (void)hipFreeAsync(dmem, s);
     return e;
   }
-  PlanArgs a;
+  PlanArgsScaled a;
   memset(&a, 0, sizeof(a));
   t.bind(a, dmem);
   a.t_begin = 0;
   a.t_end = t.units;
+  a.scale = scale;
   // the store form oneshot_cfg decided: write-through by size or on request
   // (store_policy 4), else nt
   const int pol = plan_pol(c.store == kPolStoreSys ? HICCL_PEER_STORES : 0);
@@ -50,13 +53,28 @@ int reduce_via_table(int dtype, const Cfg &c, void *out, const void *const *in, 
 
 }  // namespace
 
-extern "C" {
+namespace hiccl_impl {
 
-int hiccl_reduce_op(int dtype, int op, void *out, const void *const *in, int n, size_t count,
-                    void *stream, const hiccl_reduce_config_t *cfg) {
+int check_scale(int dtype, double alpha, const std::string &who, Scale *scale) {
   const size_t esz = esize(dtype);
-  if (!esz) return fail(hipErrorInvalidValue, "hiccl_reduce: unknown dtype " + std::to_string(dtype));
-  if (int e = check_op(dtype, cfg ? cfg->acc : HICCL_ACC_NATIVE, op, "hiccl_reduce")) return e;
+  if (!esz) return fail(hipErrorInvalidValue, who + ": unknown dtype " + std::to_string(dtype));
+  if (dtype != HICCL_FLOAT32 && dtype != HICCL_FLOAT64 && dtype != HICCL_BFLOAT16 && dtype != HICCL_FLOAT16)
+    return fail(hipErrorInvalidValue, who + ": scaled sums take the floating types only (HICCL_FLOAT32, HICCL_FLOAT64, "
+                                            "HICCL_BFLOAT16, HICCL_FLOAT16)");
+  if (!std::isfinite(alpha)) return fail(hipErrorInvalidValue, who + ": alpha must be finite");
+  const float a32 = (float)alpha;  // round to nearest even
+  if (dtype != HICCL_FLOAT64 && !std::isfinite(a32))
+    return fail(hipErrorInvalidValue, who + ": alpha must be finite as a float ((float)alpha overflows)");
+  if (scale) *scale = Scale{alpha, a32, 0u};
+  return 0;
+}
+
+// hiccl_reduce_op (scale NULL: `op` is a hiccl_op_t the caller has checked) and
+// hiccl_reduce_scaled (op == kOpScaledSum).
+int reduce_call(int dtype, int op, const Scale *scale, void *out, const void *const *in, int n, size_t count,
+                void *stream, const hiccl_reduce_config_t *cfg) {
+  const size_t esz = esize(dtype);
+  const Scale sc = scale ? *scale : Scale{0.0, 0.0f, 0u};
   if (count == 0) return 0;
   if (dtype == HICCL_BYTES && n != 1) return fail(hipErrorInvalidValue, "hiccl_reduce: HICCL_BYTES copies need n == 1");
   if (int e = check_buffers(out, in, n, count, esz)) return e;
@@ -74,7 +92,7 @@ int hiccl_reduce_op(int dtype, int op, void *out, const void *const *in, int n, 
     if (capturing(s, false))
       return fail(hipErrorStreamCaptureUnsupported,
                   "hiccl_reduce: n > 64 inputs cannot be captured into a graph (use a plan)");
-    return reduce_via_table(dtype, c, out, in, n, count, s);
+    return reduce_via_table(dtype, c, sc, out, in, n, count, s);
   }
 
   single_fn fn = single_for(dtype, c);
@@ -86,7 +104,7 @@ int hiccl_reduce_op(int dtype, int op, void *out, const void *const *in, int n, 
                                           std::to_string(c.store) + ", engine " +
                                           std::to_string(c.engine) + ") for this dtype");
 
-  SingleArgs a;
+  SingleArgsScaled a;
   memset(&a, 0, sizeof(a));
   a.out = (char *)out;
   a.npkt = sp.npkt;
@@ -95,6 +113,7 @@ int hiccl_reduce_op(int dtype, int op, void *out, const void *const *in, int n, 
   a.n = (uint32_t)n;
   a.ntiles = tiles_for(sp.npkt, (uint64_t)c.block * c.unroll);
   for (int k = 0; k < n; k++) a.in[k] = (const char *)in[k];
+  a.scale = sc;
 
   LaunchShape L = launch_shape(c, n, a.ntiles, device_cus(dev), /*paced=*/true);
   a.sched = L.dynamic ? ticket_counter(dev, s) : nullptr;
@@ -106,6 +125,50 @@ int hiccl_reduce_op(int dtype, int op, void *out, const void *const *in, int n, 
   a.order = log2u(c.order);
   fn(a, dim3((unsigned)L.grid), s);
   return check_hip(hipGetLastError(), "hiccl_reduce: launch");
+}
+
+}  // namespace hiccl_impl
+
+namespace {
+
+// hiccl_reduce_auto_choice_op and _scaled, the operator checked by the caller.
+int auto_choice(int dtype, int op, const hiccl_reduce_config_t *cfg, size_t count, double n, int cus, int *engine,
+                int *unroll, int *blocks_per_cu, int *dynamic, int *store_policy) {
+  const size_t esz = esize(dtype);
+  if (cus <= 0 || n < 0) return fail(hipErrorInvalidValue, "auto_choice: cus must be > 0 and n >= 0");
+  if (int e = check_cfg(cfg, "auto_choice")) return e;
+  CusOverride scoped(cus);  // no device query: the choice for `cus` CUs
+  const uint64_t npkt = (uint64_t)count * esz / kPacket;
+  const Cfg c = oneshot_cfg(dtype, op, cfg, npkt, (uint64_t)count * esz, n, -1);
+  // the same refusals as hiccl_reduce_ex: a shape no kernel has is an error
+  const bool has = n > kMaxArgInputs ? plan_shape_error(c, dtype).empty() : single_for(dtype, c) != nullptr;
+  if (!has) return fail(hipErrorInvalidValue, "auto_choice: no kernel for this config and dtype");
+  const uint64_t units = tiles_for(npkt, (uint64_t)c.block * c.unroll);  // tiles or phased chunks
+  const LaunchShape L = launch_shape(c, n, units, cus, /*paced=*/n <= kMaxArgInputs);
+  if (engine) *engine = c.engine;
+  if (unroll) *unroll = c.unroll;
+  if (blocks_per_cu) *blocks_per_cu = c.bpc;
+  if (dynamic) *dynamic = L.dynamic ? 1 : 0;
+  if (store_policy) *store_policy = c.store + 1;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int hiccl_reduce_op(int dtype, int op, void *out, const void *const *in, int n, size_t count,
+                    void *stream, const hiccl_reduce_config_t *cfg) {
+  if (!esize(dtype)) return fail(hipErrorInvalidValue, "hiccl_reduce: unknown dtype " + std::to_string(dtype));
+  if (int e = check_op(dtype, cfg ? cfg->acc : HICCL_ACC_NATIVE, op, "hiccl_reduce")) return e;
+  return reduce_call(dtype, op, nullptr, out, in, n, count, stream, cfg);
+}
+
+int hiccl_reduce_scaled(int dtype, double alpha, void *out, const void *const *in, int n, size_t count,
+                        void *stream, const hiccl_reduce_config_t *cfg) {
+  Scale sc;
+  if (int e = check_scale(dtype, alpha, "hiccl_reduce_scaled", &sc)) return e;
+  return reduce_call(dtype, kOpScaledSum, &sc, out, in, n, count, stream, cfg);
 }
 
 int hiccl_reduce_ex(int dtype, void *out, const void *const *in, int n, size_t count,
@@ -136,22 +199,13 @@ int hiccl_reduce_auto_choice_op(int dtype, int op, const hiccl_reduce_config_t *
   const size_t esz = esize(dtype);
   if (!esz) return fail(hipErrorInvalidValue, "auto_choice: unknown dtype");
   if (int e = check_op(dtype, cfg ? cfg->acc : HICCL_ACC_NATIVE, op, "auto_choice")) return e;
-  if (cus <= 0 || n < 0) return fail(hipErrorInvalidValue, "auto_choice: cus must be > 0 and n >= 0");
-  if (int e = check_cfg(cfg, "auto_choice")) return e;
-  CusOverride scoped(cus);  // no device query: the choice for `cus` CUs
-  const uint64_t npkt = (uint64_t)count * esz / kPacket;
-  const Cfg c = oneshot_cfg(dtype, op, cfg, npkt, (uint64_t)count * esz, n, -1);
-  // the same refusals as hiccl_reduce_ex: a shape no kernel has is an error
-  const bool has = n > kMaxArgInputs ? plan_shape_error(c, dtype).empty() : single_for(dtype, c) != nullptr;
-  if (!has) return fail(hipErrorInvalidValue, "auto_choice: no kernel for this config and dtype");
-  const uint64_t units = tiles_for(npkt, (uint64_t)c.block * c.unroll);  // tiles or phased chunks
-  const LaunchShape L = launch_shape(c, n, units, cus, /*paced=*/n <= kMaxArgInputs);
-  if (engine) *engine = c.engine;
-  if (unroll) *unroll = c.unroll;
-  if (blocks_per_cu) *blocks_per_cu = c.bpc;
-  if (dynamic) *dynamic = L.dynamic ? 1 : 0;
-  if (store_policy) *store_policy = c.store + 1;
-  return 0;
+  return auto_choice(dtype, op, cfg, count, n, cus, engine, unroll, blocks_per_cu, dynamic, store_policy);
+}
+
+int hiccl_reduce_auto_choice_scaled(int dtype, const hiccl_reduce_config_t *cfg, size_t count, double n, int cus,
+                                    int *engine, int *unroll, int *blocks_per_cu, int *dynamic, int *store_policy) {
+  if (int e = check_scale(dtype, 1.0, "auto_choice_scaled", nullptr)) return e;
+  return auto_choice(dtype, kOpScaledSum, cfg, count, n, cus, engine, unroll, blocks_per_cu, dynamic, store_policy);
 }
 
 int hiccl_reduce_auto_choice_ex(int dtype, const hiccl_reduce_config_t *cfg, size_t count, double n, int cus,

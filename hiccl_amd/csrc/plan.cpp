@@ -46,7 +46,7 @@ bool sync_if_enqueued(std::atomic<bool> &enqueued) {
   return true;
 }
 
-int launch_plan(PlanArgs a, int dtype, const Cfg &c, double mean_n, int dev, hipStream_t s, int pol) {
+int launch_plan(PlanArgsScaled a, int dtype, const Cfg &c, double mean_n, int dev, hipStream_t s, int pol) {
   plan_fn fn = pick_plan(dtype, c.acc, c.op, c.engine, c.unroll, pol);
   if (!fn)
     return fail(hipErrorInvalidValue, pol == kDefPol ? "plan: unsupported dtype / shape"
@@ -89,7 +89,7 @@ void plan_quiesce(hiccl_reduce_plan *p) {
 // packets of packet-weighted mean `mean_n` inputs.
 Cfg plan_cfg(const hiccl_reduce_plan *p, uint64_t npkt, double mean_n) {
   Cfg c = resolve(&p->req);
-  c.op = p->op;
+  c.op = p->kernel_op();
   const bool auto_unroll = !c.unroll;
   // AUTO's engine rules follow the store form the launches take by size
   c.wt = c.store_auto && plan_store_peer(p);
@@ -142,12 +142,15 @@ int plan_upload(hiccl_reduce_plan *p, hipStream_t s) {
 
 int plan_kernel(hiccl_reduce_plan *p, hipStream_t s) {
   Cfg c = resolve(&p->req);
-  c.op = p->op;
+  c.op = p->kernel_op();
   c.engine = p->engine;
   c.unroll = p->unroll;
   c.block = p->engine == HICCL_ENGINE_PHASE ? kPhBlock : kDefBlock;
   c.bpc = p->bpc;
-  return launch_plan(p->args, p->dtype, c, p->mean_n, p->device, s, plan_pol(p->eff_peer));
+  PlanArgsScaled a;  // the plan itself is only read (hiccl_reduce_plan_enqueue from several threads)
+  (PlanArgs &)a = p->args;
+  a.scale = p->scale;
+  return launch_plan(a, p->dtype, c, p->mean_n, p->device, s, plan_pol(p->eff_peer));
 }
 
 // Upload (if needed) and launch, no bookkeeping of where the launch went.
@@ -169,6 +172,27 @@ int plan_set_field(hiccl_reduce_plan_t *p, int hiccl_reduce_config_t::*field, in
   p->req = c;
   p->dirty = true;  // (the auto engine's chunk size depends on the accumulator, too)
   return 0;
+}
+
+// Does every engine config `c` may resolve to have a plan kernel of operator
+// `op` (a hiccl_op_t or kOpScaledSum) in the shape `c` names?  Empty string if
+// so, else why not.  No device work.
+std::string plan_config_error(const hiccl_reduce_plan *p, const hiccl_reduce_config_t &c, int op) {
+  Cfg r = resolve(&c);
+  r.op = op;
+  const bool shape = c.block || c.unroll;
+  if (shape && r.engine == HICCL_ENGINE_AUTO) r.engine = HICCL_ENGINE_TILE;
+  const int engines[2] = {HICCL_ENGINE_TILE, HICCL_ENGINE_PHASE};
+  for (int eng : engines) {
+    if (r.engine != HICCL_ENGINE_AUTO && r.engine != eng) continue;
+    Cfg t = r;
+    t.engine = eng;
+    if (!t.block) t.block = eng == HICCL_ENGINE_PHASE ? kPhBlock : kDefBlock;
+    if (!t.unroll) t.unroll = eng == HICCL_ENGINE_PHASE ? phase_p(p->dtype, t.acc) : kDefUnroll;
+    const std::string why = plan_shape_error(t, p->dtype);
+    if (!why.empty()) return why;
+  }
+  return "";
 }
 
 }  // namespace
@@ -201,12 +225,41 @@ int hiccl_reduce_plan_set_acc(hiccl_reduce_plan_t *p, int acc) {
 int hiccl_reduce_plan_set_op(hiccl_reduce_plan_t *p, int op) {
   if (!p) return fail(hipErrorInvalidValue, "plan_set_op: plan is NULL");
   if (int e = check_op(p->dtype, p->req.acc, op, "plan_set_op")) return e;
+  if (p->scaled && op != HICCL_OP_SUM)
+    return fail(hipErrorInvalidValue, "plan_set_op: a scaled plan sums (HICCL_OP_SUM only): clear the scale first");
   p->op = op;
   p->dirty = true;  // (AUTO's shape depends on the operator: MAX and MIN are untuned)
   return 0;
 }
 
 int hiccl_reduce_plan_op(const hiccl_reduce_plan_t *p) { return p ? p->op : -1; }
+
+int hiccl_reduce_plan_set_scale(hiccl_reduce_plan_t *p, const double *alpha) {
+  if (!p) return fail(hipErrorInvalidValue, "plan_set_scale: plan is NULL");
+  Scale sc{0.0, 0.0f, 0u};
+  if (alpha) {
+    if (int e = check_scale(p->dtype, *alpha, "plan_set_scale", &sc)) return e;
+    if (p->op != HICCL_OP_SUM)
+      return fail(hipErrorInvalidValue, "plan_set_scale: only sums are scaled (the plan's op is not HICCL_OP_SUM)");
+    // the scaled kernels are untuned: a config that names a shape only the
+    // tuned sums have (TILE unroll 1, 2, 8, 16) is refused here, not at launch
+    const std::string why = plan_config_error(p, p->req, kOpScaledSum);
+    if (!why.empty())
+      return fail(hipErrorInvalidValue, "plan_set_scale: the plan's config names a shape the scaled kernels lack: " + why);
+  }
+  // a scaled sum is another kernel, untuned: AUTO's shape may differ.  A new
+  // alpha alone travels in the kernel arguments and needs no upload.
+  if (p->scaled != (alpha != nullptr)) p->dirty = true;
+  p->scaled = alpha != nullptr;
+  p->scale = sc;
+  return 0;
+}
+
+int hiccl_reduce_plan_scale(const hiccl_reduce_plan_t *p, double *alpha) {
+  if (!p) return -1;
+  if (p->scaled && alpha) *alpha = p->scale.a64;
+  return p->scaled ? 1 : 0;
+}
 
 int hiccl_reduce_plan_set_engine(hiccl_reduce_plan_t *p, int engine) {
   return plan_set_field(p, &hiccl_reduce_config_t::engine, engine, "plan_set_engine");
@@ -236,20 +289,8 @@ int hiccl_reduce_plan_set_config(hiccl_reduce_plan_t *p, const hiccl_reduce_conf
   if (int e = check_cfg(&c, "plan_set_config")) return e;
   if (int e = check_op(p->dtype, c.acc, p->op, "plan_set_config")) return e;
   // the shape must be one the plan kernels have, whatever engine AUTO picks
-  Cfg r = resolve(&c);
-  r.op = p->op;
-  const bool shape = c.block || c.unroll;
-  if (shape && r.engine == HICCL_ENGINE_AUTO) r.engine = HICCL_ENGINE_TILE;
-  const int engines[2] = {HICCL_ENGINE_TILE, HICCL_ENGINE_PHASE};
-  for (int eng : engines) {
-    if (r.engine != HICCL_ENGINE_AUTO && r.engine != eng) continue;
-    Cfg t = r;
-    t.engine = eng;
-    if (!t.block) t.block = eng == HICCL_ENGINE_PHASE ? kPhBlock : kDefBlock;
-    if (!t.unroll) t.unroll = eng == HICCL_ENGINE_PHASE ? phase_p(p->dtype, t.acc) : kDefUnroll;
-    const std::string why = plan_shape_error(t, p->dtype);
-    if (!why.empty()) return fail(hipErrorInvalidValue, "plan_set_config: " + why);
-  }
+  const std::string why = plan_config_error(p, c, p->kernel_op());
+  if (!why.empty()) return fail(hipErrorInvalidValue, "plan_set_config: " + why);
   p->req = c;
   p->dirty = true;
   return 0;
@@ -304,7 +345,8 @@ int hiccl_reduce_plan_launch_each(hiccl_reduce_plan_t *p, void *stream) {
   // One one-shot launch per compute, each with the engine AUTO picks for that
   // compute alone (the reference's structure, compute.h:88-91).
   for (auto &c : p->comps)
-    if (int e = hiccl_reduce_op(p->dtype, p->op, c.out, c.in.data(), (int)c.in.size(), c.count, stream, &p->req))
+    if (int e = reduce_call(p->dtype, p->kernel_op(), p->scaled ? &p->scale : nullptr, c.out, c.in.data(),
+                            (int)c.in.size(), c.count, stream, &p->req))
       return e;
   p->launched = true;
   p->last = (hipStream_t)stream;

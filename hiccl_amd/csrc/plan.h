@@ -12,6 +12,10 @@ struct hiccl_reduce_plan {
   int dtype = 0;
   int device = 0;
   int op = HICCL_OP_SUM;          // hiccl_reduce_plan_set_op
+  bool scaled = false;            // hiccl_reduce_plan_set_scale: out = alpha * sum (op stays SUM)
+  hiccl_impl::Scale scale{0.0, 0.0f, 0u};
+  // the operator the policy and the kernel tables see
+  int kernel_op() const { return scaled ? hiccl_impl::kOpScaledSum : op; }
   hiccl_reduce_config_t req;      // hiccl_reduce_plan_set_config / _set_engine / _set_acc (0 = default)
   int engine = HICCL_ENGINE_TILE;  // resolved at upload
   int unroll = hiccl_impl::kDefUnroll;  // TILE packets per lane, resolved at upload
@@ -76,7 +80,8 @@ struct DescTable {
 
 // One plan-kernel launch of `a` (desc, ptrs, unit_comp, units, stride set),
 // shaped by `c` (engine and shape resolved), in cache policy `pol`.
-int launch_plan(PlanArgs a, int dtype, const Cfg &c, double mean_n, int dev, hipStream_t s, int pol);
+// (a.scale: the scale of a scaled sum, c.op == kOpScaledSum).
+int launch_plan(PlanArgsScaled a, int dtype, const Cfg &c, double mean_n, int dev, hipStream_t s, int pol);
 
 // Before a device block is freed: no launch may still read it.  True if some
 // launch went out on a stream nobody remembered -- the device was synchronised.

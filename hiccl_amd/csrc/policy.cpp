@@ -15,6 +15,10 @@
 // every other rule applies by dtype unchanged.  No threshold below has been
 // measured for any of them; DESIGN.md section 5 records the one MAX / SUM
 // comparison (M18) and the PROD / SUM ones, f32 and uint64 (M19).
+//
+// A scaled sum (kOpScaledSum, kernels.h) is untuned in the same way, under
+// either accumulator: it takes the rules of an untuned operator of its dtype,
+// and none has been measured for it beyond M20's one f32 shape.
 #include "policy.h"
 
 namespace hiccl_impl {

@@ -15,7 +15,9 @@ struct Cfg {
   bool wt;          // the launch stores write-through by size: decided BEFORE the engine
                     // (oneshot_cfg, plan_cfg), since AUTO's engine rules differ under it
   int order;        // tile-order segments (hiccl_reduce_config_t.order; 0/1 linear)
-  int op;           // hiccl_op_t: not a config entry -- the call or the plan names it (resolve: SUM)
+  int op;           // hiccl_op_t, or kOpScaledSum (a scaled sum: untuned, like every operator but
+                    // SUM, and honours acc): not a config entry -- the call or the plan names it
+                    // (resolve: SUM)
   int pol() const { return store * 10 + nt; }
 };
 
@@ -31,6 +33,15 @@ bool known_op(int op);
 // HICCL_BYTES and HICCL_ACC_WIDE, and an integer type under the bitwise
 // operators.  Refused as `who: ...` likewise.
 int check_op(int dtype, int acc, int op, const std::string &who);
+
+// A scaled sum's dtype (floating) and alpha (finite; as a float too for the 4-
+// and 2-byte types), refused as `who: ...` likewise; *scale (may be NULL): the
+// kernels' argument.
+int check_scale(int dtype, double alpha, const std::string &who, Scale *scale);
+// The one-shot call behind hiccl_reduce_op (scale NULL, `op` checked by the
+// caller) and hiccl_reduce_scaled (op kOpScaledSum): oneshot.cpp.
+int reduce_call(int dtype, int op, const Scale *scale, void *out, const void *const *in, int n, size_t count,
+                void *stream, const hiccl_reduce_config_t *cfg);
 
 // Does a launch that writes `out_bytes` from `n` inputs per output (a plan's
 // packet-weighted mean) store write-through BY SIZE under the raw config?

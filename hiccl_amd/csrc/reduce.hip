@@ -168,14 +168,17 @@ int phase_p(int dtype, int acc) {
 }
 
 // SUM's kernels are this unit's; MAX and MIN come from reduce_ops.hip, PROD
-// and the bitwise operators from reduce_prod.hip.
+// and the bitwise operators from reduce_prod.hip, the scaled sums from
+// reduce_scale.hip.
 single_fn pick_single(int dtype, int acc, int op, int engine, int block, int unroll, int pol) {
+  if (op == kOpScaledSum) return pick_single_scale(dtype, acc, op, engine, block, unroll, pol);
   if (op >= HICCL_OP_PROD) return pick_single_prod(dtype, acc, op, engine, block, unroll, pol);
   if (op != HICCL_OP_SUM) return pick_single_maxmin(dtype, acc, op, engine, block, unroll, pol);
   return part_single<kPartSum>(dtype, acc, op, engine, block, unroll, pol);
 }
 
 plan_fn pick_plan(int dtype, int acc, int op, int engine, int unroll, int pol) {
+  if (op == kOpScaledSum) return pick_plan_scale(dtype, acc, op, engine, unroll, pol);
   if (op >= HICCL_OP_PROD) return pick_plan_prod(dtype, acc, op, engine, unroll, pol);
   if (op != HICCL_OP_SUM) return pick_plan_maxmin(dtype, acc, op, engine, unroll, pol);
   return part_plan<kPartSum>(dtype, acc, op, engine, unroll, pol);

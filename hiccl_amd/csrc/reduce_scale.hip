@@ -1,0 +1,19 @@
+// hiccl_amd/csrc/reduce_scale.hip -- the scaled-sum kernels (out = alpha *
+// sum): engine.h's one-shot and plan kernels instantiated for the six ops
+// OpF32Scaled ... OpF16WideScaled (f32, f64, bf16 and f16, the 2-byte types
+// under either accumulator), in every engine's default shape (no tuning
+// table).  A translation unit of its own, linked last, so that it compiles
+// next to the other three and their code objects stay as they are.
+#include "engine.h"
+
+namespace hiccl_impl {
+
+single_fn pick_single_scale(int dtype, int acc, int op, int engine, int block, int unroll, int pol) {
+  return part_single<kPartScale>(dtype, acc, op, engine, block, unroll, pol);
+}
+
+plan_fn pick_plan_scale(int dtype, int acc, int op, int engine, int unroll, int pol) {
+  return part_plan<kPartScale>(dtype, acc, op, engine, unroll, pol);
+}
+
+}  // namespace hiccl_impl

@@ -2,8 +2,8 @@
 // facts, synthetic inputs, stream copies, bucket allocations.
 #include "runtime.h"
 
-// 0.4.0 (0.2: HICCL_FLOAT16; 0.3: hiccl_op_t, MAX and MIN; 0.4: PROD, BAND, BOR, BXOR)
-#define HICCL_VERSION_INT 400
+// 0.5.0 (0.2: HICCL_FLOAT16; 0.3: hiccl_op_t, MAX and MIN; 0.4: PROD, BAND, BOR, BXOR; 0.5: scaled sums)
+#define HICCL_VERSION_INT 500
 
 using namespace hiccl_impl;
 

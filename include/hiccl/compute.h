@@ -17,6 +17,7 @@
 #define HICCL_COMPUTE_H
 
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -106,6 +107,7 @@ class Compute {
         const int eng = v == "tile" ? HICCL_ENGINE_TILE : v == "phase" ? HICCL_ENGINE_PHASE : HICCL_ENGINE_AUTO;
         check(hiccl_reduce_plan_set_engine(plan, eng), "plan_set_engine");
       }
+      if (scaled) check(hiccl_reduce_plan_set_scale(plan, &scale), "plan_set_scale");  // set before the first add
     }
     if (peer_inputs && !(hiccl_reduce_plan_peer(plan) & HICCL_PEER_LOADS))
       check(hiccl_reduce_plan_set_peer(plan, hiccl_reduce_plan_peer(plan) | HICCL_PEER_LOADS), "plan_set_peer");
@@ -115,13 +117,38 @@ class Compute {
 #endif
   }
 
+  // Scaled sums: every compute writes finish(sum, alpha) from the next
+  // start() on (an average: alpha = 1 / inputs) -- in the sum's own pass, the
+  // multiply once per element at store time (hiccl_reduce_plan_set_scale; the
+  // host port applies the same scale_finish after host_sum, same bits).
+  // Floating T only; alpha must be finite.  A Comm<T> schedule cannot use it
+  // yet: this is for a single-level reduction.
+  void set_scale(double alpha) {
+    static_assert(op_of<T>() == 0, "HiCCL::Compute::set_scale: only sums are scaled (T is an operator wrapper)");
+    static_assert(dtype_of<T>() == 0 || dtype_of<T>() == 1 || dtype_of<T>() == 2 || dtype_of<T>() == 6,
+                  "HiCCL::Compute::set_scale: floating element types only (float, double, bf16, f16, _Float16)");
+    if (!std::isfinite(alpha) || (!std::is_same<T, double>::value && !std::isfinite((float)alpha)))
+      CommBench::die("Compute::set_scale", "alpha must be finite");
+    scaled = true;
+    scale = alpha;
+#ifndef HICCL_PORT_HOST
+    if (plan) check(hiccl_reduce_plan_set_scale(plan, &scale), "plan_set_scale");
+#endif
+  }
+  void clear_scale() {
+    scaled = false;
+#ifndef HICCL_PORT_HOST
+    if (plan) check(hiccl_reduce_plan_set_scale(plan, nullptr), "plan_set_scale");
+#endif
+  }
+
   // compute.h:87-106: nonblocking launch of all registered computes.
   void start() {
     if (!numcomp) return;
 #ifndef HICCL_PORT_HOST
     check(hiccl_reduce_plan_launch(plan, compute_stream()), "plan_launch");
 #else
-    for (int c = 0; c < numcomp; c++) host_sum(outputbuf[c], count[c], inputbuf[c]);
+    for (int c = 0; c < numcomp; c++) host_sum(outputbuf[c], count[c], inputbuf[c], scaled, scale);
 #endif
   }
 
@@ -238,18 +265,23 @@ class Compute {
   static inline double roofline_bytes = 0;  // set by measure(warmup, numiter)
 
  private:
+  bool scaled = false;  // set_scale / clear_scale
+  double scale = 1.0;
 #ifndef HICCL_PORT_HOST
   hiccl_reduce_plan_t *plan = nullptr;
   static void check(int e, const char *what) {
     if (e) CommBench::die(what, hiccl_last_error());
   }
 #else
-  static void host_sum(T *out, size_t n, const std::vector<T *> &in) {
+  static void host_sum(T *out, size_t n, const std::vector<T *> &in, bool scaled, double alpha) {
     const int k = (int)in.size();
 #pragma omp parallel for schedule(static)
     for (size_t i = 0; i < n; i++) {
       T acc = 0;
       for (int j = 0; j < k; j++) acc += in[j][i];
+      if constexpr (op_of<T>() == 0 && (dtype_of<T>() == 0 || dtype_of<T>() == 1 || dtype_of<T>() == 2 || dtype_of<T>() == 6)) {
+        if (scaled) acc = scale_finish<T>(acc, alpha);
+      }
       out[i] = acc;
     }
   }

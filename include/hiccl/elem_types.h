@@ -1,12 +1,14 @@
 // include/hiccl/elem_types.h -- the 2-byte element types of Comm<T> /
 // Compute<T>: HiCCL::bf16 and HiCCL::f16 (storage structs whose `+=` is the
-// reference's `T acc = 0; acc += x` in that type).  Plain C++, no dependency:
+// reference's `T acc = 0; acc += x` in that type), and scale_finish<T>, the
+// finishing multiply of a scaled sum.  Plain C++, no dependency:
 // compute.h and ops.h include it, and so can a host-only test.
 #ifndef HICCL_ELEM_TYPES_H
 #define HICCL_ELEM_TYPES_H
 
 #include <cstdint>
 #include <cstring>
+#include <type_traits>
 
 namespace HiCCL {
 
@@ -105,6 +107,22 @@ struct f16 {
   }
 };
 static_assert(sizeof(f16) == 2, "f16 storage");
+
+// The finishing step of a scaled sum (Compute<T>::set_scale; the C ABI's
+// hiccl_reduce_scaled): f64 one multiply by alpha; f32 one multiply by a32 =
+// (float)alpha; bf16 / f16 widen (exact), multiply in f32 ROUNDED TO F32, then
+// round to nearest even to T -- two roundings, by definition.  `volatile`
+// keeps the f32 product a rounded float on hosts that evaluate in a wider
+// format.
+template <typename T>
+inline T scale_finish(T s, double alpha) {
+  if constexpr (std::is_same<T, double>::value) {
+    return s * alpha;
+  } else {
+    volatile float p = (float)s * (float)alpha;
+    return (T)p;
+  }
+}
 
 }  // namespace HiCCL
 

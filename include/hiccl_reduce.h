@@ -233,6 +233,54 @@ int hiccl_reduce_auto_choice_op(int dtype, int op, const hiccl_reduce_config_t *
                                 int *engine, int *unroll, int *blocks_per_cu, int *dynamic, int *store_policy);
 
 /* ----------------------------------------------------------------------
+ * Scaled sums: out[i] = finish(s[i], alpha) -- an average (alpha = 1 / n),
+ * RCCL's ncclAvg / PreMulSum, a loss scale taken out of summed gradients --
+ * in the one pass of the sum: the multiply happens once per element at store
+ * time, not per add and not in a second kernel over the output.
+ *
+ *   s[i]    exactly the SUM of the same call in the accumulator type: the
+ *           reference's in-order `T acc = 0; acc += x`, or the f32 accumulator
+ *           under HICCL_ACC_WIDE (cfg->acc is honoured).
+ *   alpha   a double; a32 = (float)alpha, rounded to nearest even.
+ *   finish  HICCL_FLOAT64           fl64(s * alpha): one IEEE multiply
+ *           HICCL_FLOAT32           fl32(s * a32): one IEEE multiply
+ *           HICCL_BFLOAT16, _FLOAT16
+ *             native                round_T(fl32(widen(s) * a32)): an f32
+ *                                   multiply ROUNDED TO F32, then rounded to
+ *                                   nearest even to T.  Two roundings: that is
+ *                                   the definition (one rounding of the exact
+ *                                   product differs on some values, and so
+ *                                   does a half multiply by (half)alpha)
+ *             HICCL_ACC_WIDE        round_T(fl32(s32 * a32)), s32 the f32
+ *                                   accumulator: accumulate in f32, scale in
+ *                                   f32, round once to T
+ * Subnormal inputs and results are kept, Inf x 0 is NaN, signs follow the sign
+ * rule; the multiply follows an add, so nothing fuses; NaN outputs compare by
+ * NaN-ness.  alpha == 1.0 still multiplies (the sum's words, NaN payloads
+ * aside).  n == 0 writes finish(+0, alpha): a zero with alpha's sign.
+ *
+ * SUM only and the floating dtypes only: HICCL_INT32, HICCL_UINT64 and
+ * HICCL_BYTES are refused.  alpha must be finite, and for the 4- and 2-byte
+ * types (float)alpha must be finite too; zero, and an alpha that underflows to
+ * zero as a float, are allowed.  Every refusal is hipErrorInvalidValue with a
+ * message, before any device work.
+ *
+ * hiccl_reduce_scaled is hiccl_reduce_ex plus the finishing step: the same
+ * checks, in-place rule, misaligned head / tail handling and n > 64 path; a
+ * call with n <= 64 can be captured into a graph (alpha travels in the kernel
+ * arguments).  Like every operator but SUM the scaled kernels have no tuning
+ * table: every engine's default shape (TILE 256 x 4, PHASE's default chunk),
+ * nt or system-scope write-through stores by the same size rule, both peer
+ * policies for plans.  A config whose shape they lack is refused, never
+ * replaced; hiccl_reduce_auto_choice_scaled answers the same way on the host.
+ * No AUTO threshold has been measured for them. */
+int hiccl_reduce_scaled(int dtype, double alpha, void *out, const void *const *in, int n,
+                        size_t count, void *stream, const hiccl_reduce_config_t *cfg);
+int hiccl_reduce_auto_choice_scaled(int dtype, const hiccl_reduce_config_t *cfg, size_t count, double n,
+                                    int cus, int *engine, int *unroll, int *blocks_per_cu, int *dynamic,
+                                    int *store_policy);
+
+/* ----------------------------------------------------------------------
  * Persistent plan: the C-ABI counterpart of the reference's Compute<T>
  * (compute.h:26-204).  A plan holds any number of registered computes and
  * launches ALL of them in ONE kernel (one launch per pipeline step instead
@@ -278,6 +326,21 @@ int hiccl_reduce_plan_set_acc(hiccl_reduce_plan_t *plan, int acc);
  * hiccl_reduce_plan_op: the operator, -1 for NULL. */
 int hiccl_reduce_plan_set_op(hiccl_reduce_plan_t *plan, int op);
 int hiccl_reduce_plan_op(const hiccl_reduce_plan_t *plan);
+/* The plan's scale (hiccl_reduce_scaled): every compute of the plan writes
+ * finish(sum, *alpha) from the next launch on, launch_each included; NULL
+ * turns it off.  May be called at any time, like set_acc (switching it on or
+ * off re-uploads at the next launch; a new alpha alone does not: it travels in
+ * the kernel arguments, and an enqueue still only reads the plan).  Refused
+ * for an integer or HICCL_BYTES plan, a non-finite alpha, a plan whose
+ * operator is not SUM, and a plan whose config names a shape the scaled
+ * kernels lack (TILE unroll 1, 2, 8 or 16: refused here, before any device
+ * work, as set_config refuses it on a scaled plan) -- and set_op to another
+ * operator is refused on a scaled plan.  hiccl_program_add_plan refuses a scaled plan: a program has no scale
+ * per compute.
+ * hiccl_reduce_plan_scale: 1 and *alpha (if not NULL) for a scaled plan, 0 for
+ * an unscaled one, -1 for NULL. */
+int hiccl_reduce_plan_set_scale(hiccl_reduce_plan_t *plan, const double *alpha);
+int hiccl_reduce_plan_scale(const hiccl_reduce_plan_t *plan, double *alpha);
 /* Engine for the plan's launches (hiccl_engine_t; default AUTO, decided from
  * the total packets of all computes at the first launch after an add). */
 int hiccl_reduce_plan_set_engine(hiccl_reduce_plan_t *plan, int engine);
@@ -384,6 +447,9 @@ int hiccl_host_pipe_reduce(hiccl_host_pipe_t *pipe, void *out, const void *const
 /* The operator of the pipe's later reductions (hiccl_op_t; default SUM);
  * refused for a HICCL_BYTES pipe, and BAND / BOR / BXOR for a floating one. */
 int hiccl_host_pipe_set_op(hiccl_host_pipe_t *pipe, int op);
+/* The scale of the pipe's later sums (hiccl_reduce_scaled; NULL: off), with
+ * hiccl_reduce_plan_set_scale's refusals. */
+int hiccl_host_pipe_set_scale(hiccl_host_pipe_t *pipe, const double *alpha);
 void hiccl_host_pipe_destroy(hiccl_host_pipe_t *pipe);
 
 /* ----------------------------------------------------------------------

@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
-"""MAX or PROD against SUM on the flagship shape, in alternating fresh processes.
+"""MAX, PROD or a scaled sum against SUM on the flagship shape, in alternating fresh processes.
 
     python tools/ops_ab.py --alternate 5 --out profiles/r09a_ops_ab.jsonl
     python tools/ops_ab.py --alternate 5 --legs sum,prod,prod_u64 --out profiles/r10a_ops_ab.jsonl
+    python tools/ops_ab.py --alternate 5 --legs scaled,sum_same_shape,sum_then_mul --out profiles/r11a_scale_ab.jsonl
     python tools/ops_ab.py --leg max            (one leg, one JSON line)
 
 The shape is config 2's: n = 8 inputs of 2^28 f32 in the bucket layout
@@ -15,6 +16,14 @@ The shape is config 2's: n = 8 inputs of 2^28 f32 in the bucket layout
     prod  likewise with HICCL_OP_PROD
     prod_u64   HICCL_OP_PROD on 8 x 2^27 uint64 (the same bytes; random words,
           held in torch.int64 tensors: the same bits for either signedness)
+    scaled   hiccl_reduce_scaled, f32, alpha = 1/8 (untuned: AUTO's answer for
+          it, hiccl_reduce_auto_choice_scaled, is recorded in the line)
+    sum_same_shape   SUM forced to the shape that answer names (engine, unroll,
+          workgroups per CU, schedule, store form): the same launch without
+          the finishing multiply
+    sum_then_mul   SUM under AUTO, then a separate in-place multiply of the
+          output by 1/8 (torch's mul_): the two passes a scaled sum replaces;
+          both kernels lie between the two events
 
 Each leg runs in a process of its own (a child started by --alternate, under a
 time limit; the parent process never opens the GPU): fill the inputs with
@@ -24,7 +33,8 @@ the bandwidth at the median ((n + 1) x count x element bytes) and a sample
 check: 4,096 seeded elements of the output against the in-order sum / product
 / the maximum of the same elements of the inputs (uniform [-1, 1): no NaN, no
 zero of either sign, so NumPy's maximum states the expected word; the uint64
-product wraps in NumPy as on the GPU).  DESIGN.md section 5, M18 and M19.
+product wraps in NumPy as on the GPU; the scaled legs: the sum times 1/8 in
+f32).  DESIGN.md section 5, M18, M19 and M20.
 """
 import argparse
 import json
@@ -33,7 +43,8 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LEGS = ["sum", "max", "min", "prod", "prod_u64"]
+LEGS = ["sum", "max", "min", "prod", "prod_u64", "scaled", "sum_same_shape", "sum_then_mul"]
+ALPHA = 0.125
 
 
 def run_leg(a):
@@ -43,8 +54,8 @@ def run_leg(a):
     import hiccl_amd
     from hiccl_amd import _lib as L
 
-    op = {"sum": L.HICCL_OP_SUM, "max": L.HICCL_OP_MAX, "min": L.HICCL_OP_MIN, "prod": L.HICCL_OP_PROD,
-          "prod_u64": L.HICCL_OP_PROD}[a.leg]
+    op = {"max": L.HICCL_OP_MAX, "min": L.HICCL_OP_MIN, "prod": L.HICCL_OP_PROD,
+          "prod_u64": L.HICCL_OP_PROD}.get(a.leg, L.HICCL_OP_SUM)
     u64 = a.leg == "prod_u64"
     count = 1 << (a.log2count - 1 if u64 else a.log2count)  # the same bytes
     tdt, esz = (torch.int64, 8) if u64 else (torch.float32, 4)
@@ -57,8 +68,25 @@ def run_leg(a):
             hiccl_amd.fill_uniform(t, 1234, k)
     torch.cuda.synchronize()
 
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    scaled_auto = same_shape = None
+    if a.leg in ("scaled", "sum_same_shape"):
+        scaled_auto = hiccl_amd.auto_choice(tdt, count, a.n, cus=cus, scale=True)
+    if a.leg == "sum_same_shape":
+        same_shape = dict(engine=scaled_auto["engine"], unroll=scaled_auto["unroll"],
+                          blocks_per_cu=scaled_auto["blocks_per_cu"], store_policy=scaled_auto["store_policy"],
+                          schedule=L.HICCL_SCHED_DYNAMIC if scaled_auto["dynamic"] else L.HICCL_SCHED_STATIC)
+
     def launch():
-        hiccl_amd.reduce(out, ins, op=op)  # SUM: hiccl_reduce itself
+        if a.leg == "scaled":
+            hiccl_amd.reduce(out, ins, scale=ALPHA)
+        elif a.leg == "sum_same_shape":
+            hiccl_amd.reduce(out, ins, config=same_shape)
+        elif a.leg == "sum_then_mul":
+            hiccl_amd.reduce(out, ins)
+            out.mul_(ALPHA)
+        else:
+            hiccl_amd.reduce(out, ins, op=op)  # SUM: hiccl_reduce itself
 
     for _ in range(a.warmup):
         launch()
@@ -75,10 +103,12 @@ def run_leg(a):
     idx = torch.from_numpy(np.random.default_rng(7).integers(0, count, 4096)).to(dev)
     got = out[idx].cpu().numpy()
     rows = np.stack([t[idx].cpu().numpy() for t in ins])
-    if a.leg == "sum":
+    if op == L.HICCL_OP_SUM:
         exp = np.zeros(len(got), np.float32)
         for r in rows:
             exp = (exp + r).astype(np.float32)
+        if a.leg in ("scaled", "sum_then_mul"):
+            exp = (exp * np.float32(ALPHA)).astype(np.float32)
     elif a.leg == "prod":
         exp = np.ones(len(got), np.float32)
         for r in rows:
@@ -94,8 +124,8 @@ def run_leg(a):
     line = {"probe": "ops_ab", "leg": a.leg, "round": a.round, "n": a.n, "count": count, "layout": "bucket",
             "warmup": a.warmup, "steps": a.steps, "median_ms": round(med, 5), "min_ms": round(times[0], 5),
             "max_ms": round(times[-1], 5), "tbps_median": round((a.n + 1) * count * esz / med / 1e9, 4),
-            "auto": hiccl_amd.auto_choice(tdt, count, a.n, op=op,
-                                          cus=torch.cuda.get_device_properties(0).multi_processor_count),
+            "auto": scaled_auto if a.leg in ("scaled", "sum_same_shape") else
+                    hiccl_amd.auto_choice(tdt, count, a.n, op=op, cus=cus),
             "sample_ok": bool(np.array_equal(got.view(word), exp.view(word))),
             "device": torch.cuda.get_device_name(0)}
     print(json.dumps(line), flush=True)
