@@ -17,7 +17,8 @@ $(PROBE): tools/hbm_probe.hip
 # The library: four kernel translation units over one header of templates
 # (engine.h) -- reduce.hip, the SUM kernels, reduce_ops.hip, the MAX / MIN
 # kernels, reduce_prod.hip, the PROD and bitwise kernels, and reduce_scale.hip,
-# the scaled sums, compiled side by
+# the scaled sums, which also takes in reduce_f8.hip, the OCP FP8 types (the
+# library keeps four code objects, the scaled sums' last), compiled side by
 # side (reduce.hip the longest) -- and the host files (seconds each), as
 # objects under build/obj, linked once.  The link order is the order of the
 # library's code objects: the SUM unit first, new units last.
@@ -76,7 +77,8 @@ CPP_BINS = build/plan_dump build/collectives_host build/collectives_host_f32 bui
            build/f16_add build/f16_compute_host build/f16_compute_hip \
            build/ops_add build/ops_compute_host build/ops_compute_hip build/ops_comm_host build/ops_comm_hip \
            build/prod_add build/prod_compute_host build/prod_compute_hip build/prod_comm_host build/prod_comm_hip \
-           build/scale_finish build/scale_compute_host build/scale_compute_hip
+           build/scale_finish build/scale_compute_host build/scale_compute_hip \
+           build/f8_add build/f8_compute_host build/f8_compute_hip
 
 cpp: $(CPP_BINS)
 
@@ -194,6 +196,22 @@ build/scale_compute_host: tests/cpp/scale_compute.cpp $(HDRS)
 	$(CXX) $(CXXFLAGS) -fopenmp -DHICCL_PORT_HOST -o $@ $< $(MPI_LINK)
 
 build/scale_compute_hip: tests/cpp/scale_compute.cpp $(HDRS) $(LIB)
+	@mkdir -p build
+	$(CXX) $(CXXFLAGS) $(HIP_HOST) -o $@ $< $(HIP_LINK) $(MPI_LINK)
+
+# OCP FP8: HiCCL::f8e4m3 / f8e5m2 -- `+=`, round, operator float and the
+# maxof / minof identities as tables (a stand-alone host program), and
+# Compute<f8e4m3> / Compute<f8e5m2>, plain and with set_scale, on the host port
+# and on the GPU (tests/test_f8_cpu.py, tests/test_f8_gpu.py)
+build/f8_add: tests/cpp/f8_add.cpp $(HDRS)
+	@mkdir -p build
+	$(CXX) $(CXXFLAGS) -o $@ $<
+
+build/f8_compute_host: tests/cpp/f8_compute.cpp $(HDRS)
+	@mkdir -p build
+	$(CXX) $(CXXFLAGS) -fopenmp -DHICCL_PORT_HOST -o $@ $< $(MPI_LINK)
+
+build/f8_compute_hip: tests/cpp/f8_compute.cpp $(HDRS) $(LIB)
 	@mkdir -p build
 	$(CXX) $(CXXFLAGS) $(HIP_HOST) -o $@ $< $(HIP_LINK) $(MPI_LINK)
 

@@ -7,6 +7,7 @@ package is the binding used by the tests and bench.py.
 """
 from ._lib import (HICCL_ACC_NATIVE, HICCL_ACC_WIDE, HICCL_BFLOAT16, HICCL_ENGINE_AUTO,  # noqa: F401
                    HICCL_ENGINE_PHASE, HICCL_ENGINE_TILE, HICCL_FLOAT16, HICCL_FLOAT32, HICCL_FLOAT64, HICCL_INT32, HICCL_UINT64,
+                   HICCL_FLOAT8_E4M3, HICCL_FLOAT8_E5M2,
                    HICCL_OP_BAND, HICCL_OP_BOR, HICCL_OP_BXOR, HICCL_OP_MAX, HICCL_OP_MIN, HICCL_OP_PROD, HICCL_OP_SUM,
                    HicclError, LIB_PATH, header_functions, lib)
 from .compute import (Compute, HostPipe, Program, auto_choice, bucket, fill_uniform, reduce, reduce_ptrs,  # noqa: F401

@@ -25,6 +25,8 @@ HICCL_UINT64 = 3
 HICCL_INT32 = 4
 HICCL_BYTES = 5
 HICCL_FLOAT16 = 6
+HICCL_FLOAT8_E4M3 = 16  # OCP FP8; 7-15 are no dtype
+HICCL_FLOAT8_E5M2 = 17
 
 HICCL_ACC_NATIVE = 0
 HICCL_ACC_WIDE = 1
@@ -55,6 +57,8 @@ DTYPE_OF_TORCH = {
     torch.float64: HICCL_FLOAT64,
     torch.bfloat16: HICCL_BFLOAT16,
     torch.float16: HICCL_FLOAT16,
+    torch.float8_e4m3fn: HICCL_FLOAT8_E4M3,
+    torch.float8_e5m2: HICCL_FLOAT8_E5M2,
     torch.int64: HICCL_UINT64,  # two's-complement add == size_t add bit for bit
     torch.uint64: HICCL_UINT64,
     torch.int32: HICCL_INT32,

@@ -37,6 +37,9 @@ def _dtype_code(t):
         raise TypeError(f"hiccl: unsupported dtype {t.dtype}") from None
 
 
+_FP8 = (torch.float8_e4m3fn, torch.float8_e5m2)  # OCP FP8: SUM (scaled too), MAX and MIN only
+
+
 def _check_op(op, dtype):
     """torch.int64 stands for size_t under the sign-agnostic operators (SUM,
     PROD and the bitwise three: the same bits for either signedness); MAX and
@@ -46,6 +49,8 @@ def _check_op(op, dtype):
         raise TypeError("hiccl: MAX / MIN on HICCL_UINT64 compare unsigned: pass torch.uint64, not torch.int64")
     if op in (L.HICCL_OP_BAND, L.HICCL_OP_BOR, L.HICCL_OP_BXOR) and dtype.is_floating_point:
         raise TypeError(f"hiccl: BAND / BOR / BXOR take the integer types only (int32, uint64), not {dtype}")
+    if op == L.HICCL_OP_PROD and dtype in _FP8:
+        raise TypeError(f"hiccl: PROD is not defined for the FP8 types, not {dtype}")
 
 
 def _check_scale(scale, dtype, op=L.HICCL_OP_SUM):
@@ -53,11 +58,12 @@ def _check_scale(scale, dtype, op=L.HICCL_OP_SUM):
     SUM, a finite scale -- refused here, before any device work.  Returns the
     scale as a float."""
     if isinstance(dtype, torch.dtype):
-        floating = dtype in (torch.float32, torch.float64, torch.bfloat16, torch.float16)
+        floating = dtype in (torch.float32, torch.float64, torch.bfloat16, torch.float16) + _FP8
     else:
-        floating = int(dtype) in (L.HICCL_FLOAT32, L.HICCL_FLOAT64, L.HICCL_BFLOAT16, L.HICCL_FLOAT16)
+        floating = int(dtype) in (L.HICCL_FLOAT32, L.HICCL_FLOAT64, L.HICCL_BFLOAT16, L.HICCL_FLOAT16,
+                                  L.HICCL_FLOAT8_E4M3, L.HICCL_FLOAT8_E5M2)
     if not floating:
-        raise TypeError(f"hiccl: scaled sums take the floating types only (f32, f64, bf16, f16), not {dtype}")
+        raise TypeError(f"hiccl: scaled sums take the floating types only (f32, f64, bf16, f16, fp8), not {dtype}")
     if op != L.HICCL_OP_SUM:
         raise ValueError("hiccl: only sums are scaled: scale= goes with HICCL_OP_SUM")
     if isinstance(scale, torch.Tensor) and scale.ndim == 0 and not scale.is_complex():

@@ -2,11 +2,12 @@
 // shares: the element ops, the TILE and PHASE engines, the unit schedules, the
 // one-shot / plan / program kernels and their instantiation tables.
 //
-// The library's kernels are compiled as four translation units that run side
+// The library's kernels are compiled as five translation units that run side
 // by side in the build: reduce.hip instantiates the tables for the SUM ops
 // (kPartSum), reduce_ops.hip for the MAX / MIN ops (kPartMaxMin),
-// reduce_prod.hip for PROD and the bitwise ops (kPartProd) and
-// reduce_scale.hip for the post-scaled sums (kPartScale).  All
+// reduce_prod.hip for PROD and the bitwise ops (kPartProd),
+// reduce_scale.hip for the post-scaled sums (kPartScale) and reduce_f8.hip
+// for every op of the two OCP FP8 types (kPartF8).  All
 // take their ops from the one list below (with_elem<PART>), so a type or an
 // operator is still added in one place.  Everything here is in an anonymous
 // namespace: a kernel belongs to the unit that instantiates it.
@@ -594,6 +595,229 @@ typedef OpBF16Scaled<OpBF16> OpBF16NatScaled;
 typedef OpBF16Scaled<OpBF16Wide> OpBF16WideScaled;
 typedef OpF16Scaled<OpF16> OpF16NatScaled;
 typedef OpF16Scaled<OpF16Wide> OpF16WideScaled;
+
+// -------------------------------------------------------------- OCP FP8 ops --
+// HICCL_FLOAT8_E4M3 (e4m3fn) and HICCL_FLOAT8_E5M2, 16 elements per packet.
+// The arithmetic is defined through f32 (hiccl_reduce.h): widen(b) is exact,
+// round_F(x) clamps a FINITE x to [-max, +max] (saturate-to-finite) and rounds
+// to nearest even, subnormals kept; a NaN stays a NaN, +-Inf stays +-Inf in
+// e5m2 and becomes a NaN in e4m3.
+// gfx950 converts two elements per instruction: v_cvt_pk_f32_fp8 / _bf8 widen
+// the low or the high half of a word, v_cvt_pk_fp8_f32 / _bf8_f32 round two
+// f32 into one half of a word and keep the other.  The clamp comes FIRST and
+// is this code's own, so nothing rests on what the conversion does with a
+// finite value out of range; Inf and NaN reach it unclamped.
+// The native ops keep the accumulator PACKED (16 elements in a u32x4, the
+// packet's own layout, 4 VGPRs), as OpBF16 does and for its reason: the phased
+// engine then runs FP8 at the same 128 KiB chunk as f32.  Per packet a native
+// add is 16 widens (8 of the accumulator, 8 of the input), 16 f32 adds, the
+// clamp (e4m3: 32 instructions, e5m2: 48) and 8 rounds.
+constexpr int kE4M3 = 0, kE5M2 = 1;
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+template <int FMT>
+struct F8 {
+  static constexpr float kMax = FMT == kE4M3 ? 448.0f : 57344.0f;
+  // the operator identities: e5m2 -Inf / +Inf, e4m3 (no infinity) -448 / +448
+  static constexpr uint32_t kMaxId = FMT == kE4M3 ? 0xfeu : 0xfcu;
+  static constexpr uint32_t kMinId = FMT == kE4M3 ? 0x7eu : 0x7cu;
+  // bytes {0, 1} (hi = false) or {2, 3} of w, exact
+  template <bool HI>
+  __device__ static f32x2 widen2(uint32_t w) {
+    if constexpr (FMT == kE4M3) return __builtin_amdgcn_cvt_pk_f32_fp8((int)w, HI);
+    else return __builtin_amdgcn_cvt_pk_f32_bf8((int)w, HI);
+  }
+  // The clamp of round_F.  INF = false: the caller knows x is finite or NaN
+  // (a sum of two e4m3 values: the format has no infinity) -- the IEEE
+  // 754-2019 maximum / minimum pair, which passes a NaN on.  Otherwise the
+  // median of a finite x, and a non-finite x as it is.
+  template <bool INF>
+  __device__ static float clamp(float x) {
+    if constexpr (!INF) return fmm<false>(fmm<true>(x, -kMax), kMax);
+    else return __builtin_isfinite(x) ? __builtin_amdgcn_fmed3f(x, -kMax, kMax) : x;
+  }
+  // round_F(lo), round_F(hi) into the low or the high half of `old`
+  template <bool HI, bool INF>
+  __device__ static uint32_t round2(float lo, float hi, uint32_t old) {
+    lo = clamp<INF>(lo);
+    hi = clamp<INF>(hi);
+    if constexpr (FMT == kE4M3) return (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(lo, hi, (int)old, HI);
+    else return (uint32_t)__builtin_amdgcn_cvt_pk_bf8_f32(lo, hi, (int)old, HI);
+  }
+  // one element (the peeled head / tail)
+  __device__ static float widen1(uint8_t b) { return widen2<false>(b)[0]; }
+  template <bool INF>
+  __device__ static uint8_t round1(float x) { return (uint8_t)round2<false, INF>(x, x, 0u); }
+  __device__ static float ld(const char *p) { return widen1(gld<uint8_t>(p)); }
+};
+
+// the 16 elements of a packet <-> f32, four per word
+template <int FMT>
+__device__ __forceinline__ void f8_widen4(uint32_t w, float (&v)[4]) {
+  const f32x2 lo = F8<FMT>::template widen2<false>(w), hi = F8<FMT>::template widen2<true>(w);
+  v[0] = lo[0], v[1] = lo[1], v[2] = hi[0], v[3] = hi[1];
+}
+template <int FMT, bool INF>
+__device__ __forceinline__ uint32_t f8_round4(const float (&v)[4]) {
+  const uint32_t r = F8<FMT>::template round2<false, INF>(v[0], v[1], 0u);
+  return F8<FMT>::template round2<true, INF>(v[2], v[3], r);
+}
+
+// Native SUM: acc = round_F(fl32(widen(acc) + widen(x))) after every input.
+// Both operands of e4m3 are finite or NaN, so is their f32 sum: no Inf select.
+template <int FMT>
+struct OpF8 {
+  static constexpr bool kWidens = true;
+  static constexpr int kEsz = 1;
+  static constexpr bool kInf = FMT == kE5M2;
+  typedef u32x4 acc_t;
+  __device__ static acc_t zero() { return (u32x4)(0u); }  // +0
+  __device__ static acc_t add(acc_t a, u32x4 p) {
+    acc_t r;
+#pragma unroll
+    for (int w = 0; w < 4; w++) {
+      float x[4], y[4];
+      f8_widen4<FMT>(a[w], x);
+      f8_widen4<FMT>(p[w], y);
+#pragma unroll
+      for (int i = 0; i < 4; i++) x[i] += y[i];
+      r[w] = f8_round4<FMT, kInf>(x);
+    }
+    return r;
+  }
+  __device__ static u32x4 pack(acc_t a) { return a; }
+  typedef float sacc_t;  // a widened element
+  __device__ static sacc_t szero() { return 0.0f; }
+  __device__ static sacc_t sadd(sacc_t a, const char *p) {
+    return F8<FMT>::widen1(F8<FMT>::template round1<kInf>(a + F8<FMT>::ld(p)));
+  }
+  __device__ static void sstore(char *p, sacc_t a) { gst<uint8_t>(p, F8<FMT>::template round1<true>(a)); }
+};
+
+// HICCL_ACC_WIDE: an f32 accumulator per element (16 VGPRs per packet), one
+// f32 add per input in list order from +0, round_F once at the end.
+template <int FMT>
+struct OpF8Wide {
+  static constexpr bool kWidens = true;
+  static constexpr int kEsz = 1;
+  // sixteen floats, not a 16-wide vector: one 512-bit register tuple per packet
+  // made the tile kernels spill (copies of whole tuples around the group loop)
+  struct acc_t {
+    float v[16];
+    __device__ float &operator[](int i) { return v[i]; }
+  };
+  __device__ static acc_t zero() {
+    acc_t a;
+#pragma unroll
+    for (int i = 0; i < 16; i++) a.v[i] = 0.0f;
+    return a;
+  }
+  __device__ static acc_t add(acc_t a, u32x4 p) {
+#pragma unroll
+    for (int w = 0; w < 4; w++) {
+      float y[4];
+      f8_widen4<FMT>(p[w], y);
+#pragma unroll
+      for (int i = 0; i < 4; i++) a[4 * w + i] += y[i];
+    }
+    return a;
+  }
+  __device__ static u32x4 pack(acc_t a) {
+    u32x4 r;
+#pragma unroll
+    for (int w = 0; w < 4; w++) {
+      const float x[4] = {a[4 * w], a[4 * w + 1], a[4 * w + 2], a[4 * w + 3]};
+      r[w] = f8_round4<FMT, true>(x);
+    }
+    return r;
+  }
+  typedef float sacc_t;
+  __device__ static sacc_t szero() { return 0.0f; }
+  __device__ static sacc_t sadd(sacc_t a, const char *p) { return a + F8<FMT>::ld(p); }
+  __device__ static void sstore(char *p, sacc_t a) { gst<uint8_t>(p, F8<FMT>::template round1<true>(a)); }
+};
+
+// MAX / MIN: IEEE 754-2019 maximum / minimum of the widened values, packed
+// again by the rounding conversion -- the winner is an FP8 value, so nothing
+// rounds and nothing needs the clamp (e5m2's infinities pass the conversion as
+// they are).  A NaN operand gives a NaN, -0 < +0.
+template <bool MAX, int FMT>
+struct OpF8MM {
+  static constexpr bool kWidens = true;
+  static constexpr int kEsz = 1;
+  static constexpr uint32_t kIdByte = MAX ? F8<FMT>::kMaxId : F8<FMT>::kMinId;
+  static constexpr uint32_t kIdBits = kIdByte * 0x01010101u;
+  typedef u32x4 acc_t;
+  __device__ static acc_t zero() { return (u32x4)(kIdBits); }
+  // not an inline constant: from a scalar register, as OpBF16MM's
+  __device__ static acc_t tile_zero() {
+    uint32_t k;
+    asm("s_mov_b32 %0, %1" : "=s"(k) : "i"(kIdBits));
+    return (u32x4)(k);
+  }
+  __device__ static uint32_t join(const float (&v)[4]) {
+    uint32_t r;
+    if constexpr (FMT == kE4M3) {
+      r = (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(v[0], v[1], 0, false);
+      r = (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(v[2], v[3], (int)r, true);
+    } else {
+      r = (uint32_t)__builtin_amdgcn_cvt_pk_bf8_f32(v[0], v[1], 0, false);
+      r = (uint32_t)__builtin_amdgcn_cvt_pk_bf8_f32(v[2], v[3], (int)r, true);
+    }
+    return r;
+  }
+  __device__ static acc_t add(acc_t a, u32x4 p) {
+    acc_t r;
+#pragma unroll
+    for (int w = 0; w < 4; w++) {
+      float x[4], y[4];
+      f8_widen4<FMT>(a[w], x);
+      f8_widen4<FMT>(p[w], y);
+#pragma unroll
+      for (int i = 0; i < 4; i++) x[i] = fmm<MAX>(x[i], y[i]);
+      r[w] = join(x);
+    }
+    return r;
+  }
+  __device__ static u32x4 pack(acc_t a) { return a; }
+  typedef float sacc_t;  // a widened element
+  __device__ static sacc_t szero() { return F8<FMT>::widen1((uint8_t)kIdByte); }
+  __device__ static sacc_t sadd(sacc_t a, const char *p) { return fmm<MAX>(a, F8<FMT>::ld(p)); }
+  __device__ static void sstore(char *p, sacc_t a) {
+    const float v[4] = {a, a, a, a};
+    gst<uint8_t>(p, (uint8_t)join(v));
+  }
+};
+
+// Scaled sums: Base = OpF8 (round_F(fl32(widen(s) * a32))) or OpF8Wide
+// (round_F(fl32(s32 * a32))).  The f32 product may overflow to Inf, so the
+// rounding takes the full clamp.
+template <class Base, int FMT>
+struct OpF8Scaled : Base {
+  typedef float fin_t;
+  __device__ static float fin(const Scale &s) { return s.a32; }
+  __device__ static u32x4 pack(typename Base::acc_t a, float a32) {
+    u32x4 r;
+#pragma unroll
+    for (int w = 0; w < 4; w++) {
+      float x[4];
+      if constexpr (sizeof(typename Base::acc_t) > kPacket) {
+#pragma unroll
+        for (int i = 0; i < 4; i++) x[i] = a[4 * w + i];
+      } else {
+        f8_widen4<FMT>(a[w], x);
+      }
+#pragma unroll
+      for (int i = 0; i < 4; i++) x[i] = scale_f32(x[i], a32);
+      r[w] = f8_round4<FMT, true>(x);
+    }
+    return r;
+  }
+  // the scalar accumulator of both is a float (native: a widened element)
+  __device__ static void sstore(char *p, float a, float a32) {
+    gst<uint8_t>(p, F8<FMT>::template round1<true>(scale_f32(a, a32)));
+  }
+};
 
 // ----------------------------------------------------------- tile engine --
 //
@@ -1295,6 +1519,7 @@ constexpr int kPartSum = 0;
 constexpr int kPartMaxMin = 1;
 constexpr int kPartProd = 2;  // PROD, BAND, BOR, BXOR
 constexpr int kPartScale = 3;  // post-scaled sums (kOpScaledSum)
+constexpr int kPartF8 = 4;  // the OCP FP8 types, every operator they have
 
 // MAX and MIN of the six arithmetic types; HICCL_BYTES has no operator.
 template <bool MAX, class R, class F>
@@ -1368,9 +1593,39 @@ R with_elem_scale(int dtype, int acc, R unknown, F f) {
   }
 }
 
+// The two OCP FP8 types: every operator they have -- SUM under either
+// accumulator, MAX, MIN and the scaled sums -- is one part (kPartF8,
+// reduce_f8.hip), and the lists above do not know the types.  Untuned.
+inline bool is_f8(int dtype) { return dtype == HICCL_FLOAT8_E4M3 || dtype == HICCL_FLOAT8_E5M2; }
+
+template <int FMT, int DT, class R, class F>
+R with_elem_f8_fmt(int acc, int op, R unknown, F f) {
+  const bool wide = acc == HICCL_ACC_WIDE;
+  switch (op) {
+    case HICCL_OP_SUM: return wide ? f(Elem<DT, OpF8Wide<FMT>, false>()) : f(Elem<DT, OpF8<FMT>, false>());
+    case kOpScaledSum:
+      return wide ? f(Elem<DT, OpF8Scaled<OpF8Wide<FMT>, FMT>, false>())
+                  : f(Elem<DT, OpF8Scaled<OpF8<FMT>, FMT>, false>());
+    case HICCL_OP_MAX: return wide ? unknown : f(Elem<DT, OpF8MM<true, FMT>, false>());
+    case HICCL_OP_MIN: return wide ? unknown : f(Elem<DT, OpF8MM<false, FMT>, false>());
+    default: return unknown;  // no PROD and no bitwise operator on FP8
+  }
+}
+
+template <class R, class F>
+R with_elem_f8(int dtype, int acc, int op, R unknown, F f) {
+  switch (dtype) {
+    case HICCL_FLOAT8_E4M3: return with_elem_f8_fmt<kE4M3, HICCL_FLOAT8_E4M3>(acc, op, unknown, f);
+    case HICCL_FLOAT8_E5M2: return with_elem_f8_fmt<kE5M2, HICCL_FLOAT8_E5M2>(acc, op, unknown, f);
+    default: return unknown;
+  }
+}
+
 template <int PART, class R, class F>
 R with_elem(int dtype, int acc, int op, R unknown, F f) {
-  if constexpr (PART == kPartScale) {
+  if constexpr (PART == kPartF8) {
+    return with_elem_f8(dtype, acc, op, unknown, f);
+  } else if constexpr (PART == kPartScale) {
     return op == kOpScaledSum ? with_elem_scale(dtype, acc, unknown, f) : unknown;
   } else if constexpr (PART == kPartProd) {
     if (acc != HICCL_ACC_NATIVE) return unknown;
@@ -1395,7 +1650,8 @@ R with_elem(int dtype, int acc, int op, R unknown, F f) {
 
 // P of the phased engine: 16 packets per lane (acc + two in-flight loads =
 // 3 x 64 VGPRs at 512 lanes) unless the accumulator is wider than a packet
-// (bf16 / f16 wide: f32x8) or the compiler reassociates the adds and holds more
+// (bf16 / f16 wide: 8 floats; FP8 wide: 16 floats -- 128 VGPRs of accumulators
+// and two loads of 32 in flight, 222 VGPRs as compiled) or the compiler reassociates the adds and holds more
 // registers (int32: exact, so it may) -- then 8.  The chunk is a property of
 // (dtype, acc): int32 takes 8 under every operator, so the host sizes a plan's
 // units without asking for the operator.

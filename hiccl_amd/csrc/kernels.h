@@ -181,12 +181,18 @@ prog_fn pick_prog_prod(int dtype, int op, int unroll);
 // the scaled sums (reduce_scale.hip; op == kOpScaledSum): no program kernels
 single_fn pick_single_scale(int dtype, int acc, int op, int engine, int block, int unroll, int pol);
 plan_fn pick_plan_scale(int dtype, int acc, int op, int engine, int unroll, int pol);
+// the two OCP FP8 types under every operator they have (reduce_f8.hip): SUM,
+// MAX, MIN and kOpScaledSum (which has no program kernel)
+single_fn pick_single_f8(int dtype, int acc, int op, int engine, int block, int unroll, int pol);
+plan_fn pick_plan_f8(int dtype, int acc, int op, int engine, int unroll, int pol);
+prog_fn pick_prog_f8(int dtype, int op, int unroll);
 
 // ---- the plain kernels
 
 void launch_sigwait_phases(const SigPhaseArgs &a, hipStream_t s);
 void launch_counter_add(uint32_t *ctr, uint32_t v, hipStream_t s);
-// false: no fill kernel for this dtype (FLOAT32 / FLOAT64 / BFLOAT16 / FLOAT16 only)
+// false: no fill kernel for this dtype (the floating types only: FLOAT32 /
+// FLOAT64 / BFLOAT16 / FLOAT16 / FLOAT8_E4M3 / FLOAT8_E5M2)
 bool launch_fill(int dtype, unsigned blocks, hipStream_t s, char *out, uint64_t count, uint64_t key, uint64_t first);
 void launch_copy(unsigned blocks, hipStream_t s, void *dst, const void *src, uint64_t npkt);
 void launch_copy_bytes(hipStream_t s, char *dst, const char *src, uint64_t nbytes);

@@ -58,9 +58,10 @@ namespace hiccl_impl {
 int check_scale(int dtype, double alpha, const std::string &who, Scale *scale) {
   const size_t esz = esize(dtype);
   if (!esz) return fail(hipErrorInvalidValue, who + ": unknown dtype " + std::to_string(dtype));
-  if (dtype != HICCL_FLOAT32 && dtype != HICCL_FLOAT64 && dtype != HICCL_BFLOAT16 && dtype != HICCL_FLOAT16)
+  if (dtype != HICCL_FLOAT32 && dtype != HICCL_FLOAT64 && dtype != HICCL_BFLOAT16 && dtype != HICCL_FLOAT16 &&
+      dtype != HICCL_FLOAT8_E4M3 && dtype != HICCL_FLOAT8_E5M2)
     return fail(hipErrorInvalidValue, who + ": scaled sums take the floating types only (HICCL_FLOAT32, HICCL_FLOAT64, "
-                                            "HICCL_BFLOAT16, HICCL_FLOAT16)");
+                                            "HICCL_BFLOAT16, HICCL_FLOAT16, HICCL_FLOAT8_E4M3, HICCL_FLOAT8_E5M2)");
   if (!std::isfinite(alpha)) return fail(hipErrorInvalidValue, who + ": alpha must be finite");
   const float a32 = (float)alpha;  // round to nearest even
   if (dtype != HICCL_FLOAT64 && !std::isfinite(a32))

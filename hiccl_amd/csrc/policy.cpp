@@ -19,6 +19,13 @@
 // A scaled sum (kOpScaledSum, kernels.h) is untuned in the same way, under
 // either accumulator: it takes the rules of an untuned operator of its dtype,
 // and none has been measured for it beyond M20's one f32 shape.
+//
+// The OCP FP8 types (HICCL_FLOAT8_E4M3, HICCL_FLOAT8_E5M2) are untuned under
+// every operator and either accumulator: they take the rules f64 takes (no
+// wide or half-size tile, no rule of the tuned types), with their own chunk
+// (phase_p: 16 packets native, 8 with the f32 accumulator).  No threshold
+// below has been measured for FP8; DESIGN.md section 5 (M21) records the one
+// FP8 / bf16 comparison.
 #include "policy.h"
 
 namespace hiccl_impl {
@@ -240,6 +247,9 @@ int check_op(int dtype, int acc, int op, const std::string &who) {
   if (bitwise && esize(dtype) && dtype != HICCL_INT32 && dtype != HICCL_UINT64)
     return fail(hipErrorInvalidValue,
                 who + ": HICCL_OP_BAND / _BOR / _BXOR take the integer types only (HICCL_INT32, HICCL_UINT64)");
+  if (op == HICCL_OP_PROD && (dtype == HICCL_FLOAT8_E4M3 || dtype == HICCL_FLOAT8_E5M2))
+    return fail(hipErrorInvalidValue,
+                who + ": HICCL_OP_PROD is not defined for the FP8 types (HICCL_FLOAT8_E4M3, HICCL_FLOAT8_E5M2)");
   return 0;
 }
 

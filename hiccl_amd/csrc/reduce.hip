@@ -35,7 +35,8 @@
 //
 // The engines and kernels are templates in engine.h.  This file instantiates
 // them for the SUM ops and holds the plain kernels (fills, copies, stream
-// signalling); reduce_ops.hip instantiates them for MAX and MIN.  The host
+// signalling); reduce_ops.hip instantiates them for MAX and MIN, reduce_f8.hip
+// for the two OCP FP8 types.  The host
 // files (policy.cpp: the AUTO rules; oneshot.cpp, plan.cpp, ...: the C ABI)
 // see both through kernels.h.
 
@@ -67,6 +68,9 @@ __global__ __launch_bounds__(256) void k_fill(char *out, uint64_t count, uint64_
     if constexpr (DT == HICCL_FLOAT64) ((double *)out)[i] = (double)v;
     if constexpr (DT == HICCL_BFLOAT16) ((uint16_t *)out)[i] = bf_round(v);
     if constexpr (DT == HICCL_FLOAT16) ((uint16_t *)out)[i] = f16_round(v);
+    // FP8: the same f32 value under round_F (|v| <= 1, so the clamp is idle)
+    if constexpr (DT == HICCL_FLOAT8_E4M3) ((uint8_t *)out)[i] = F8<kE4M3>::round1<true>(v);
+    if constexpr (DT == HICCL_FLOAT8_E5M2) ((uint8_t *)out)[i] = F8<kE5M2>::round1<true>(v);
   }
 }
 
@@ -155,22 +159,26 @@ __global__ __launch_bounds__(64) void k_counter_add(uint32_t *ctr, uint32_t v) {
 namespace hiccl_impl {
 
 size_t esize(int dtype) {
+  if (is_f8(dtype)) return OpF8<kE4M3>::kEsz;
   return with_elem_sum(dtype, HICCL_ACC_NATIVE, (size_t)0, [](auto e) { return (size_t)decltype(e)::Op::kEsz; });
 }
 
 bool tuned_type(int dtype, int acc, int op) {
-  // no MAX / MIN, PROD or bitwise op is tuned (engine.h's list), so the other parts are not asked
+  // no MAX / MIN, PROD or bitwise op and no FP8 type is tuned (engine.h's list), so the other parts are not asked
   return part_tuned<kPartSum>(dtype, acc, op);
 }
 
 int phase_p(int dtype, int acc) {
+  if (is_f8(dtype)) return acc == HICCL_ACC_WIDE ? phase_p_of<OpF8Wide<kE4M3>>() : phase_p_of<OpF8<kE4M3>>();
   return with_elem_sum(dtype, acc, 16, [](auto e) { return phase_p_of<typename decltype(e)::Op>(); });
 }
 
 // SUM's kernels are this unit's; MAX and MIN come from reduce_ops.hip, PROD
 // and the bitwise operators from reduce_prod.hip, the scaled sums from
-// reduce_scale.hip.
+// reduce_scale.hip; the FP8 types' kernels, whatever the operator, from
+// reduce_f8.hip.
 single_fn pick_single(int dtype, int acc, int op, int engine, int block, int unroll, int pol) {
+  if (is_f8(dtype)) return pick_single_f8(dtype, acc, op, engine, block, unroll, pol);
   if (op == kOpScaledSum) return pick_single_scale(dtype, acc, op, engine, block, unroll, pol);
   if (op >= HICCL_OP_PROD) return pick_single_prod(dtype, acc, op, engine, block, unroll, pol);
   if (op != HICCL_OP_SUM) return pick_single_maxmin(dtype, acc, op, engine, block, unroll, pol);
@@ -178,6 +186,7 @@ single_fn pick_single(int dtype, int acc, int op, int engine, int block, int unr
 }
 
 plan_fn pick_plan(int dtype, int acc, int op, int engine, int unroll, int pol) {
+  if (is_f8(dtype)) return pick_plan_f8(dtype, acc, op, engine, unroll, pol);
   if (op == kOpScaledSum) return pick_plan_scale(dtype, acc, op, engine, unroll, pol);
   if (op >= HICCL_OP_PROD) return pick_plan_prod(dtype, acc, op, engine, unroll, pol);
   if (op != HICCL_OP_SUM) return pick_plan_maxmin(dtype, acc, op, engine, unroll, pol);
@@ -185,6 +194,7 @@ plan_fn pick_plan(int dtype, int acc, int op, int engine, int unroll, int pol) {
 }
 
 prog_fn pick_prog(int dtype, int op, int unroll) {
+  if (is_f8(dtype)) return pick_prog_f8(dtype, op, unroll);
   if (op >= HICCL_OP_PROD) return pick_prog_prod(dtype, op, unroll);
   if (op != HICCL_OP_SUM) return pick_prog_maxmin(dtype, op, unroll);
   return part_prog<kPartSum>(dtype, op, unroll);
@@ -199,6 +209,13 @@ void launch_counter_add(uint32_t *ctr, uint32_t v, hipStream_t s) {
 }
 
 bool launch_fill(int dtype, unsigned blocks, hipStream_t s, char *out, uint64_t count, uint64_t key, uint64_t first) {
+  if (dtype == HICCL_FLOAT8_E4M3 || dtype == HICCL_FLOAT8_E5M2) {
+    if (dtype == HICCL_FLOAT8_E4M3)
+      hipLaunchKernelGGL(k_fill<HICCL_FLOAT8_E4M3>, dim3(blocks), dim3(256), 0, s, out, count, key, first);
+    else
+      hipLaunchKernelGGL(k_fill<HICCL_FLOAT8_E5M2>, dim3(blocks), dim3(256), 0, s, out, count, key, first);
+    return true;
+  }
   return with_elem_sum(dtype, HICCL_ACC_NATIVE, false, [&](auto e) {
     typedef decltype(e) E;
     // the floating types: f32, f64, bf16, f16

@@ -4,6 +4,10 @@
 // under either accumulator), in every engine's default shape (no tuning
 // table).  A translation unit of its own, linked last, so that it compiles
 // next to the other three and their code objects stay as they are.
+//
+// The kernels of the two OCP FP8 types (reduce_f8.hip) are compiled into this
+// unit too, behind the scaled sums': the library stays at four code objects
+// with this one last, which the ISA tier of the scaled sums relies on.
 #include "engine.h"
 
 namespace hiccl_impl {
@@ -17,3 +21,5 @@ plan_fn pick_plan_scale(int dtype, int acc, int op, int engine, int unroll, int 
 }
 
 }  // namespace hiccl_impl
+
+#include "reduce_f8.hip"

@@ -2,8 +2,9 @@
 // facts, synthetic inputs, stream copies, bucket allocations.
 #include "runtime.h"
 
-// 0.5.0 (0.2: HICCL_FLOAT16; 0.3: hiccl_op_t, MAX and MIN; 0.4: PROD, BAND, BOR, BXOR; 0.5: scaled sums)
-#define HICCL_VERSION_INT 500
+// 0.6.0 (0.2: HICCL_FLOAT16; 0.3: hiccl_op_t, MAX and MIN; 0.4: PROD, BAND, BOR, BXOR; 0.5: scaled sums;
+// 0.6: HICCL_FLOAT8_E4M3, HICCL_FLOAT8_E5M2)
+#define HICCL_VERSION_INT 600
 
 using namespace hiccl_impl;
 
@@ -31,7 +32,7 @@ int hiccl_fill_uniform(int dtype, void *out, size_t count, uint64_t seed, uint32
   const uint64_t cap = (uint64_t)device_cus(current_device()) * 16;
   if (blocks > cap) blocks = cap;
   if (!launch_fill(dtype, (unsigned)blocks, (hipStream_t)stream, (char *)out, (uint64_t)count, key, (uint64_t)first))
-    return fail(hipErrorInvalidValue, "fill_uniform: dtype must be FLOAT32/FLOAT64/BFLOAT16/FLOAT16");
+    return fail(hipErrorInvalidValue, "fill_uniform: dtype must be FLOAT32/FLOAT64/BFLOAT16/FLOAT16/FLOAT8_E4M3/FLOAT8_E5M2");
   return check_hip(hipGetLastError(), "fill_uniform: launch");
 }
 

@@ -34,7 +34,8 @@
 
 namespace HiCCL {
 
-// bf16 and f16, the 2-byte storage types: elem_types.h.  maxof<U>, minof<U>,
+// bf16 and f16, the 2-byte storage types, and f8e4m3 and f8e5m2, the 1-byte
+// ones (OCP FP8): elem_types.h.  maxof<U>, minof<U>,
 // prodof<U>, bandof<U>, borof<U>, bxorof<U>, the types whose `+=` is another
 // operator: ops.h.
 
@@ -48,11 +49,16 @@ constexpr int dtype_of() {
   else if constexpr (std::is_integral<T>::value && sizeof(T) == 4) return 4;
   else if constexpr (std::is_same<T, bf16>::value) return 2;
   else if constexpr (std::is_same<T, f16>::value) return 6;
+  else if constexpr (std::is_same<T, f8e4m3>::value) return 16;  // HICCL_FLOAT8_E4M3
+  else if constexpr (std::is_same<T, f8e5m2>::value) return 17;  // HICCL_FLOAT8_E5M2
 #ifdef __FLT16_MANT_DIG__  // the compiler has _Float16: its `+=` is the half add itself
   else if constexpr (std::is_same<T, _Float16>::value) return 6;
 #endif
   else return -1;
 }
+
+// the dtypes a scaled sum takes: the floating ones
+constexpr bool scalable_dtype(int d) { return d == 0 || d == 1 || d == 2 || d == 6 || d == 16 || d == 17; }
 
 #ifndef HICCL_PORT_HOST
 // One compute stream per process (see transport_stream()).
@@ -125,8 +131,9 @@ class Compute {
   // yet: this is for a single-level reduction.
   void set_scale(double alpha) {
     static_assert(op_of<T>() == 0, "HiCCL::Compute::set_scale: only sums are scaled (T is an operator wrapper)");
-    static_assert(dtype_of<T>() == 0 || dtype_of<T>() == 1 || dtype_of<T>() == 2 || dtype_of<T>() == 6,
-                  "HiCCL::Compute::set_scale: floating element types only (float, double, bf16, f16, _Float16)");
+    static_assert(scalable_dtype(dtype_of<T>()),
+                  "HiCCL::Compute::set_scale: floating element types only (float, double, bf16, f16, _Float16, "
+                  "f8e4m3, f8e5m2)");
     if (!std::isfinite(alpha) || (!std::is_same<T, double>::value && !std::isfinite((float)alpha)))
       CommBench::die("Compute::set_scale", "alpha must be finite");
     scaled = true;
@@ -279,7 +286,7 @@ class Compute {
     for (size_t i = 0; i < n; i++) {
       T acc = 0;
       for (int j = 0; j < k; j++) acc += in[j][i];
-      if constexpr (op_of<T>() == 0 && (dtype_of<T>() == 0 || dtype_of<T>() == 1 || dtype_of<T>() == 2 || dtype_of<T>() == 6)) {
+      if constexpr (op_of<T>() == 0 && scalable_dtype(dtype_of<T>())) {
         if (scaled) acc = scale_finish<T>(acc, alpha);
       }
       out[i] = acc;

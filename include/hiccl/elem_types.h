@@ -1,5 +1,6 @@
-// include/hiccl/elem_types.h -- the 2-byte element types of Comm<T> /
-// Compute<T>: HiCCL::bf16 and HiCCL::f16 (storage structs whose `+=` is the
+// include/hiccl/elem_types.h -- the 2-byte and 1-byte element types of Comm<T>
+// / Compute<T>: HiCCL::bf16, HiCCL::f16 and the OCP FP8 pair HiCCL::f8e4m3 /
+// f8e5m2 (storage structs whose `+=` is the
 // reference's `T acc = 0; acc += x` in that type), and scale_finish<T>, the
 // finishing multiply of a scaled sum.  Plain C++, no dependency:
 // compute.h and ops.h include it, and so can a host-only test.
@@ -107,6 +108,78 @@ struct f16 {
   }
 };
 static_assert(sizeof(f16) == 2, "f16 storage");
+
+// OCP FP8 storage types for Comm<T> / Compute<T>, shaped like bf16 above:
+// f8e4m3 (e4m3fn: bias 7, largest finite value 448, no infinities, NaN is
+// (b & 0x7f) == 0x7f; HICCL_FLOAT8_E4M3) and f8e5m2 (bias 15, largest finite
+// value 57344, infinities 0x7c / 0xfc, NaN above them; HICCL_FLOAT8_E5M2).
+// `operator float` is the exact value.  round(f): a NaN gives a NaN, +-Inf
+// gives +-Inf in e5m2 and a NaN in e4m3, a finite f is clamped to [-max, +max]
+// (saturate to finite) and then rounded to nearest even, subnormals kept, and
+// a magnitude of at most half the smallest subnormal gives a zero with f's
+// sign.  `+=` is the reference's `T acc = 0; acc += x` in that type: widen
+// both (exact), add in f32, round -- the bits of the GPU kernels
+// (HICCL_ACC_NATIVE).
+template <bool E5M2>
+struct fp8 {
+  static constexpr int kMan = E5M2 ? 2 : 3, kBias = E5M2 ? 15 : 7;
+  static constexpr uint32_t kMaxF32 = E5M2 ? 0x47600000u : 0x43e00000u;  // 57344.0f / 448.0f
+  uint8_t bits = 0;
+  fp8() = default;
+  fp8(int v) : bits(round((float)v)) {}  // T acc = 0
+  explicit fp8(float f) : bits(round(f)) {}
+  bool isnan() const { return E5M2 ? (bits & 0x7fu) > 0x7cu : (bits & 0x7fu) == 0x7fu; }
+  explicit operator float() const {
+    const uint32_t sign = (uint32_t)(bits & 0x80u) << 24;
+    const uint32_t e = (bits & 0x7fu) >> kMan, m = bits & ((1u << kMan) - 1u);
+    uint32_t w;
+    if (isnan()) {
+      w = sign | 0x7fc00000u;
+    } else if (E5M2 && e == 0x1fu) {
+      w = sign | 0x7f800000u;
+    } else if (e) {
+      w = sign | ((e + 127u - kBias) << 23) | (m << (23 - kMan));
+    } else {  // zero or subnormal: m * 2^(1 - bias - man), exact in f32
+      const float sub = (float)m * (E5M2 ? 1.52587890625e-05f : 0.001953125f);  // 2^-16 / 2^-9
+      std::memcpy(&w, &sub, 4);
+      w |= sign;
+    }
+    float f;
+    std::memcpy(&f, &w, 4);
+    return f;
+  }
+  fp8 &operator+=(fp8 o) {
+    bits = round((float)*this + (float)o);
+    return *this;
+  }
+  bool operator==(fp8 o) const { return bits == o.bits; }
+  bool operator!=(fp8 o) const { return bits != o.bits; }
+  static uint8_t round(float f) {
+    uint32_t w;
+    std::memcpy(&w, &f, 4);
+    const uint8_t sign = (uint8_t)((w >> 24) & 0x80u);
+    uint32_t a = w & 0x7fffffffu;
+    if (a > 0x7f800000u) return (uint8_t)(sign | 0x7fu);                    // NaN
+    if (a == 0x7f800000u) return (uint8_t)(sign | (E5M2 ? 0x7cu : 0x7fu));  // Inf: e4m3 has none
+    if (a > kMaxF32) a = kMaxF32;                                           // saturate to finite
+    constexpr int sh = 23 - kMan;
+    if (a >= ((uint32_t)(128 - kBias) << 23)) {  // a normal FP8 value (>= 2^(1 - bias)); a carry out of the
+                                                 // mantissa moves into the exponent, never past the maximum
+      const uint32_t r = a - ((uint32_t)(127 - kBias) << 23) + ((1u << (sh - 1)) - 1u) + ((a >> sh) & 1u);
+      return (uint8_t)(sign | (r >> sh));
+    }
+    // below half the smallest subnormal, 2^(-bias - man): zero (the half itself ties to even, zero)
+    if (a < ((uint32_t)(127 - kBias - kMan) << 23)) return sign;
+    // subnormal: the 24-bit significand shifted down to units of 2^(1 - bias - man)
+    const uint32_t e = a >> 23, sig = (a & 0x7fffffu) | 0x800000u;
+    const uint32_t shift = 151u - kBias - kMan - e;  // 21..24 (e4m3), 22..24 (e5m2)
+    const uint32_t q = sig >> shift, rem = sig & ((1u << shift) - 1u), half = 1u << (shift - 1);
+    return (uint8_t)(sign | (q + ((rem > half || (rem == half && (q & 1u))) ? 1u : 0u)));
+  }
+};
+typedef fp8<false> f8e4m3;
+typedef fp8<true> f8e5m2;
+static_assert(sizeof(f8e4m3) == 1 && sizeof(f8e5m2) == 1, "fp8 storage");
 
 // The finishing step of a scaled sum (Compute<T>::set_scale; the C ABI's
 // hiccl_reduce_scaled): f64 one multiply by alpha; f32 one multiply by a32 =

@@ -17,6 +17,9 @@
 //   float, double, bf16, f16, _Float16   IEEE 754-2019 maximum / minimum: a
 //       NaN operand gives NaN, -0 < +0, subnormals are kept, nothing rounds;
 //       identity -Inf (maxof) / +Inf (minof).
+//   f8e4m3, f8e5m2 (maxof / minof only)   the same maximum / minimum; identity
+//       -Inf / +Inf for e5m2, -448 / +448 (0xfe / 0x7e) for e4m3, which has
+//       no infinity.  prodof and the bitwise wrappers of them do not compile.
 //   signed 4-byte integers     signed compare, INT32_MIN / INT32_MAX.
 //   unsigned 8-byte integers   unsigned compare, 0 / UINT64_MAX.
 // prodof (identity 1): float, double, _Float16 -- one multiply in U per `+=`;
@@ -45,6 +48,13 @@ template <class U> struct half_bits : std::false_type {};
 template <> struct half_bits<bf16> : std::true_type { static constexpr uint16_t inf = 0x7f80u; };
 template <> struct half_bits<f16> : std::true_type { static constexpr uint16_t inf = 0x7c00u; };
 
+// the two 1-byte storage structs (OCP FP8): ordered through their bit patterns
+// too.  e5m2's identities are its infinities; e4m3fn has none and takes its
+// largest finite values, -448 (0xfe) for a maximum and +448 (0x7e) for a minimum.
+template <class U> struct f8_bits : std::false_type {};
+template <> struct f8_bits<f8e4m3> : std::true_type { static constexpr uint8_t top = 0x7eu; };
+template <> struct f8_bits<f8e5m2> : std::true_type { static constexpr uint8_t top = 0x7cu; };
+
 template <class U>
 constexpr bool is_float_like() {
 #ifdef __FLT16_MANT_DIG__
@@ -71,6 +81,10 @@ U identity() {
       U r;
       r.bits = (uint16_t)(half_bits<U>::inf | (MAX ? 0x8000u : 0u));
       return r;
+    } else if constexpr (f8_bits<U>::value) {
+      U r;
+      r.bits = (uint8_t)(f8_bits<U>::top | (MAX ? 0x80u : 0u));
+      return r;
     } else if constexpr (std::is_integral<U>::value) {
       return MAX ? std::numeric_limits<U>::min() : std::numeric_limits<U>::max();
     } else {
@@ -86,12 +100,22 @@ inline int half_key(uint16_t bits) {
   return (bits & 0x8000u) ? -mag - 1 : mag;
 }
 
+inline int f8_key(uint8_t bits) {
+  const int mag = bits & 0x7f;
+  return (bits & 0x80u) ? -mag - 1 : mag;
+}
+
 template <bool MAX, class U>
 U fold_mm(U a, U b) {
   if constexpr (half_bits<U>::value) {
     if ((a.bits & 0x7fffu) > half_bits<U>::inf) return a;  // NaN
     if ((b.bits & 0x7fffu) > half_bits<U>::inf) return b;
     const int ka = half_key(a.bits), kb = half_key(b.bits);
+    return MAX ? (ka < kb ? b : a) : (kb < ka ? b : a);
+  } else if constexpr (f8_bits<U>::value) {
+    if (a.isnan()) return a;
+    if (b.isnan()) return b;
+    const int ka = f8_key(a.bits), kb = f8_key(b.bits);
     return MAX ? (ka < kb ? b : a) : (kb < ka ? b : a);
   } else if constexpr (std::is_integral<U>::value) {
     return MAX ? (a < b ? b : a) : (b < a ? b : a);
@@ -136,8 +160,12 @@ struct wrap {
   typedef U value_type;
   static constexpr int hiccl_op = (int)OP;  // HICCL_OP_MAX ... HICCL_OP_BXOR
   static constexpr bool kMM = OP == tag::max || OP == tag::min;
-  static_assert(half_bits<U>::value || is_float_like<U>() || std::is_integral<U>::value,
-                "HiCCL::maxof / minof / prodof: U must be float, double, bf16, f16, int32 or uint64");
+  static_assert(half_bits<U>::value || f8_bits<U>::value || is_float_like<U>() || std::is_integral<U>::value,
+                "HiCCL::maxof / minof / prodof: U must be float, double, bf16, f16, int32 or uint64 "
+                "(maxof / minof: f8e4m3 and f8e5m2 too)");
+  static_assert(kMM || !f8_bits<U>::value,
+                "HiCCL::prodof / bandof / borof / bxorof: the FP8 types (f8e4m3, f8e5m2) have a sum, a maximum "
+                "and a minimum only");
   // dtype_of maps every 8-byte integer to HICCL_UINT64 (sums, products and
   // the bitwise operators wrap alike) and every 4-byte integer to
   // HICCL_INT32; a maximum is not sign-agnostic

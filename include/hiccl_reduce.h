@@ -41,8 +41,38 @@ typedef enum {
   HICCL_INT32 = 4,
   HICCL_BYTES = 5,  /* exact copy, exactly one input: out = in[0] (transport data movement) */
   HICCL_FLOAT16 = 6, /* IEEE binary16 */
-  HICCL_NUM_DTYPES = 7
+  HICCL_NUM_DTYPES = 7, /* counts the dense block 0-6 only: 7-15 are no dtype */
+  HICCL_FLOAT8_E4M3 = 16, /* OCP FP8 e4m3fn (torch.float8_e4m3fn), below */
+  HICCL_FLOAT8_E5M2 = 17  /* OCP FP8 e5m2 (torch.float8_e5m2), below */
 } hiccl_dtype_t;
+
+/* OCP FP8 (the formats gfx950 converts in hardware; not the fnuz encodings).
+ * One byte per element, 1-byte alignment for every pointer.  F is either:
+ *   e4m3fn  bias 7, largest finite value 448, no infinities, NaN is
+ *           (b & 0x7f) == 0x7f.
+ *   e5m2    bias 15, largest finite value 57344, infinities 0x7c / 0xfc, NaN
+ *           is (b & 0x7f) > 0x7c.
+ * widen(b) is the exact f32 value of b.  round_F(x) of an f32 x: a NaN gives a
+ * NaN of F (NaN outputs compare by NaN-ness); +-Inf gives +-Inf in e5m2 and a
+ * NaN in e4m3; a finite x is first clamped to [-max, +max] (saturate to
+ * finite) and then rounded to nearest even, subnormals of F kept, and a
+ * magnitude up to half the smallest subnormal gives a zero with x's sign.
+ *   SUM, native   acc = +0; per input, in list order,
+ *                 acc = round_F(fl32(widen(acc) + widen(x))) -- the reference's
+ *                 `T acc = 0; acc += x` with T = F.  All -0 inputs give +0,
+ *                 448 + 448 gives 448, e5m2 Inf + -Inf gives NaN, n == 0
+ *                 writes +0.
+ *   SUM, HICCL_ACC_WIDE   an f32 accumulator from +0, one f32 add per input in
+ *                 list order, round_F once at the end.
+ *   scaled sums   native round_F(fl32(widen(s) * a32)), WIDE
+ *                 round_F(fl32(s32 * a32)), a32 = (float)alpha as for bf16.
+ *   MAX, MIN      IEEE 754-2019 maximum / minimum of the widened values: the
+ *                 result is one of the inputs, a NaN propagates, -0 < +0.
+ *                 Identities (n == 0 writes them): e5m2 -Inf / +Inf; e4m3 has
+ *                 no infinity and takes 0xfe (-448) / 0x7e (+448).
+ *   PROD, BAND, BOR, BXOR are refused (hipErrorInvalidValue), as is WIDE with
+ *   MAX or MIN.
+ * Untuned: every engine's default shape, as every operator but SUM. */
 
 /* Accumulation mode (only meaningful for the 2-byte float types,
  * HICCL_BFLOAT16 and HICCL_FLOAT16). */
