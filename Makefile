@@ -78,7 +78,8 @@ CPP_BINS = build/plan_dump build/collectives_host build/collectives_host_f32 bui
            build/ops_add build/ops_compute_host build/ops_compute_hip build/ops_comm_host build/ops_comm_hip \
            build/prod_add build/prod_compute_host build/prod_compute_hip build/prod_comm_host build/prod_comm_hip \
            build/scale_finish build/scale_compute_host build/scale_compute_hip \
-           build/f8_add build/f8_compute_host build/f8_compute_hip
+           build/f8_add build/f8_compute_host build/f8_compute_hip \
+           build/types_comm_host build/types_comm_hip
 
 cpp: $(CPP_BINS)
 
@@ -212,6 +213,17 @@ build/f8_compute_host: tests/cpp/f8_compute.cpp $(HDRS)
 	$(CXX) $(CXXFLAGS) -fopenmp -DHICCL_PORT_HOST -o $@ $< $(MPI_LINK)
 
 build/f8_compute_hip: tests/cpp/f8_compute.cpp $(HDRS) $(LIB)
+	@mkdir -p build
+	$(CXX) $(CXXFLAGS) $(HIP_HOST) -o $@ $< $(HIP_LINK) $(MPI_LINK)
+
+# Comm<T> for every element type and operator wrapper: the eight collectives
+# on raw bytes, judged by tests/comm_expected.py (tests/test_types_comm_cpu.py,
+# tests/test_types_comm_gpu.py)
+build/types_comm_host: tests/cpp/types_comm.cpp $(HDRS)
+	@mkdir -p build
+	$(CXX) $(CXXFLAGS) -fopenmp -DHICCL_PORT_HOST -o $@ $< $(MPI_LINK)
+
+build/types_comm_hip: tests/cpp/types_comm.cpp $(HDRS) $(LIB)
 	@mkdir -p build
 	$(CXX) $(CXXFLAGS) $(HIP_HOST) -o $@ $< $(HIP_LINK) $(MPI_LINK)
 

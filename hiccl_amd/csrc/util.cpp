@@ -59,7 +59,9 @@ int hiccl_device_info(int device, int *cus, int *mem_clock_khz, int *bus_width_b
 int hiccl_stream_copy(void *dst, const void *src, size_t bytes, void *stream) {
   if (bytes == 0) return 0;
   if (!dst || !src) return fail(hipErrorInvalidValue, "stream_copy: NULL pointer");
-  if ((uintptr_t)dst % 16 || (uintptr_t)src % 16)
+  // the packet loop needs aligned pointers; fewer than 16 bytes are the byte tail alone, at any address (the
+  // transport's probe of an IPC mapping reads 8 bytes or fewer where a buffer of 1- or 2-byte elements starts)
+  if (bytes >= 16 && ((uintptr_t)dst % 16 || (uintptr_t)src % 16))
     return fail(hipErrorInvalidValue, "stream_copy: pointers must be 16-B aligned");
   hipStream_t s = (hipStream_t)stream;
   const uint64_t npkt = bytes / 16;

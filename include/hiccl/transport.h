@@ -378,6 +378,7 @@ struct IpcExport {
   hipIpcMemHandle_t handle;
   uint64_t base;    // peer's allocation base (identifies the mapping)
   uint64_t offset;  // byte offset of the buffer inside that allocation
+  uint64_t size;    // bytes of that allocation
   uint64_t nonce;   // probe value written at the buffer (probe != 0), see ipc_probe_*
   uint32_t probe;   // bytes of the probe (0: no probe)
   uint32_t recycled;  // the base was exported before for another allocation
@@ -524,6 +525,7 @@ inline IpcExport ipc_export(const void *p, int to) {
   hip_check(hipIpcGetMemHandle(&e.handle, (void *)base), "hipIpcGetMemHandle");
   e.base = (uint64_t)(uintptr_t)base;
   e.offset = (uint64_t)((const char *)p - (const char *)base);
+  e.size = (uint64_t)size;
   unsigned long long id = 0;
   if (hipPointerGetAttribute(&id, HIP_POINTER_ATTRIBUTE_BUFFER_ID, base) != hipSuccess) {
     (void)hipGetLastError();
@@ -565,10 +567,14 @@ inline uint64_t ipc_probe_begin(IpcExport &e, void *p, size_t bytes) {
   return saved;
 }
 // 0: both views see the nonce; bit 0: the copy engine's view differs; bit 1:
-// a kernel's view (what the transfers use) differs.
-inline int ipc_probe_check(const IpcExport &e, const void *mapped, std::string *seen = nullptr) {
-  uint64_t got = 0, got_k = 0;
-  hip_check(hipMemcpy(&got, mapped, e.probe, hipMemcpyDeviceToHost), "probe read");
+// a kernel's view (what the transfers use) differs.  `room`: bytes from
+// `mapped` to the end of the mapping as the runtime records it; hipMemcpy
+// refuses a read past that ("invalid argument"), so where the record is
+// shorter than the probe (ipc_import: a mapping kept from a smaller buffer)
+// the kernel's view, the one the transfers use, is the one checked.
+inline int ipc_probe_check(const IpcExport &e, const void *mapped, size_t room, std::string *seen = nullptr) {
+  uint64_t got = e.nonce, got_k = 0;
+  if (room >= e.probe) hip_check(hipMemcpy(&got, mapped, e.probe, hipMemcpyDeviceToHost), "probe read");
   static uint64_t *scratch = nullptr;
   if (!scratch) hip_check(hipMalloc((void **)&scratch, 64), "probe scratch");
   if (hiccl_stream_copy(scratch, mapped, e.probe, nullptr)) die("probe", hiccl_last_error());
@@ -603,6 +609,17 @@ inline void ipc_trim() {
   while (!ipc_retired().empty()) ipc_close_oldest_retired();
 }
 
+// Bytes of the allocation mapped at `ptr` as the runtime knows it (0: unknown).
+inline size_t ipc_mapped_bytes(void *ptr) {
+  hipDeviceptr_t mb = nullptr;
+  size_t bytes = 0;
+  if (hipMemGetAddressRange(&mb, &bytes, (hipDeviceptr_t)ptr) != hipSuccess) {
+    (void)hipGetLastError();
+    bytes = 0;
+  }
+  return bytes;
+}
+
 // The mapping of peer's exported buffer; its key is appended to `held`,
 // which the holder hands to ipc_release when it no longer uses the mapping.
 inline char *ipc_import(int peer, const IpcExport &e, std::vector<IpcKey> &held) {
@@ -622,11 +639,30 @@ inline char *ipc_import(int peer, const IpcExport &e, std::vector<IpcKey> &held)
     } else {
       void *ptr = nullptr;
       hip_check(hipIpcOpenMemHandle(&ptr, e.handle, hipIpcMemLazyEnablePeerAccess), "hipIpcOpenMemHandle");
-      hipDeviceptr_t mb = nullptr;
-      size_t bytes = 0;
-      if (hipMemGetAddressRange(&mb, &bytes, (hipDeviceptr_t)ptr) != hipSuccess) {
-        (void)hipGetLastError();
-        bytes = 0;
+      size_t bytes = ipc_mapped_bytes(ptr);
+      if (bytes && bytes < e.size) {
+        // The peer freed a small buffer and allocated a LARGER one at its
+        // address (communicators over buffers of growing sizes: a 4-byte
+        // stage buffer, then one of 2734 bytes).  Small allocations are
+        // fragments of one block of the peer's allocator, a mapping is of the
+        // whole block, and while the retired mapping of the freed fragment is
+        // open the runtime resolves the new handle to it: the same pointer,
+        // recorded at the OLD size.  The memory is reached (the probe of this
+        // recycled export verifies it with a kernel); only the runtime's
+        // record is short, so host copies past it are refused
+        // (ipc_probe_check).  Closing the retired mappings and opening the
+        // handle again is no way out: it fails now and then on ROCm 7.2
+        // ("hipIpcOpenMemHandle: invalid device pointer", the behaviour the
+        // retirement exists for).  Any other short mapping stops the job
+        // before a kernel runs past it.
+        bool kept = false;
+        for (const IpcRetired &old : r) kept = kept || (old.key.rank == k.rank && old.key.base == k.base && old.ptr == ptr);
+        if (ipc_debug())
+          ipc_note("[ipc %d] peer %d base %#llx: mapping recorded at %zu B for an allocation of %llu B%s\n", myid, peer,
+                   (unsigned long long)e.base, bytes, (unsigned long long)e.size, kept ? " (a retired mapping's)" : "");
+        if (!kept || !e.recycled)
+          die("transport", "the IPC mapping of rank " + std::to_string(peer) + "'s buffer covers " + std::to_string(bytes) +
+                           " of its " + std::to_string(e.size) + " bytes");
       }
       it = m.emplace(k, IpcMapping{(char *)ptr, 0, bytes}).first;
       ipc_live_bytes() += bytes;
@@ -955,7 +991,8 @@ class Comm {
         x.remote = ipc_import(owner, e, held);
         if (e.probe) {
           std::string seen;
-          int bad = ipc_probe_check(e, x.remote, &seen);
+          const size_t have = ipc_opened().at(IpcKey{owner, (uintptr_t)e.base}).bytes;  // 0: unknown
+          int bad = ipc_probe_check(e, x.remote, !have ? SIZE_MAX : have > e.offset ? have - (size_t)e.offset : 0, &seen);
           int ok = bad == 0;
           if (ipc_debug()) ipc_note("[ipc %d] probe peer %d base %#llx: %d\n", myid, owner,
                                     (unsigned long long)e.base, bad);

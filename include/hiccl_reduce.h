@@ -608,7 +608,8 @@ int hiccl_step_program_default(void);
  * (dtypes FLOAT32, BFLOAT16, FLOAT64; FLOAT16: the same f32 value rounded to
  * nearest-even half).
  * stream_copy: plain 16-byte-per-lane device copy, the achievable-bandwidth
- * ceiling reference for the roofline.
+ * ceiling reference for the roofline.  Pointers 16-byte aligned; a copy of
+ * fewer than 16 bytes takes any address.
  */
 int hiccl_fill_uniform(int dtype, void *out, size_t count, uint64_t seed, uint32_t k,
                        size_t first, void *stream);

@@ -424,22 +424,35 @@ class Remote(tuple):
     reduce: the transfer that fed this input was dropped).  Remote((rank, loc))."""
 
 
-def simulate(steps, numproc, user, dtype=np.float32):
+def simulate(steps, numproc, user, dtype=np.float32, add=None):
     """Execute the plan.  user: {(rank, name): array}.  Temporaries are
     created on first write.  Comms of a step run before its computes (the
     reference's run(): every library's comm waits before that library's
     compute starts, and distinct batches of a step never touch the same
-    bytes).  A compute is reduce_kernel: acc = 0; acc += in[k] in list order."""
+    bytes).  A compute is reduce_kernel: acc = 0; acc += in[k] in list order.
+    add(acc, x) -> acc: the element type's `+=` on arrays of `dtype`, for
+    types NumPy has no arithmetic for (bf16 / FP8 bit patterns in uint16 /
+    uint8: all-zero bits are the +0 the accumulator starts from); the default
+    is NumPy's add rounded to `dtype`."""
     mem = {k: v.copy() for k, v in user.items()}
+    dtype = np.dtype(dtype)
+    if add is None:
+        def add(acc, x):
+            return (acc + x).astype(dtype)
+
+    def unwritten(n):  # a float NaN, or all-ones bytes (a NaN in bf16 / FP8 bit patterns)
+        if dtype.kind == "f":
+            return np.full(n, np.nan, dtype)
+        return np.frombuffer(b"\xff" * (n * dtype.itemsize), dtype).copy()
 
     def view(rank, loc, count):
         buf, off = loc
         key = (rank, buf)
         if key not in mem:  # temporaries start as NaN: reading one before it is written shows
-            mem[key] = np.full(max(off + count, 1), np.nan, dtype)
+            mem[key] = unwritten(max(off + count, 1))
         arr = mem[key]
         if len(arr) < off + count:
-            arr = np.concatenate([arr, np.full(off + count - len(arr), np.nan, dtype)])
+            arr = np.concatenate([arr, unwritten(off + count - len(arr))])
             mem[key] = arr
         return arr, off
 
@@ -455,7 +468,7 @@ def simulate(steps, numproc, user, dtype=np.float32):
                     acc = np.zeros(cnt, dtype)
                     for loc in ins:
                         a, o = view(*loc, cnt) if isinstance(loc, Remote) else view(r, loc, cnt)
-                        acc = (acc + a[o:o + cnt]).astype(dtype)
+                        acc = add(acc, a[o:o + cnt])
                     oa, oo = view(r, out, cnt)
                     oa[oo:oo + cnt] = acc
     return mem

@@ -101,6 +101,21 @@ def test_allreduce_float_bits_vs_oracle(tmp_path, oracle, np_, count, stripe, ri
     batched plan (these shapes would pick the tile engine).  Graph mode runs
     the pipeline 4 times (eager, capture + replay, 2 replays) and checks the
     last replay's bits."""
+    _allreduce_float_bits(tmp_path, oracle, np_, count, stripe, ring, depth, hier, libs, streamed, fused, engine, graph)
+
+
+@pytest.mark.parametrize("streamed,fused,engine", [
+    (True, False, "auto"), (False, False, "auto"), (True, True, "auto"), (False, True, "auto"), (False, False, "phase"),
+    (True, True, "phase")], ids=["stream", "host", "stream-fused", "host-fused", "host-phase", "stream-fused-phase"])
+def test_allreduce_float_bits_vs_oracle_striped(tmp_path, oracle, streamed, fused, engine):
+    """The numstripe = 2 row of tests/test_mpi_host.py's twin of the test
+    above, in its six modes without graph replay: the 8 ranks of this row run
+    with the lowered hardware-queue count (mpirun), which new tests do not
+    combine with the replay of a captured graph."""
+    _allreduce_float_bits(tmp_path, oracle, 8, 4099, 2, 1, 2, "2,4", "mpi,ipc", streamed, fused, engine, False)
+
+
+def _allreduce_float_bits(tmp_path, oracle, np_, count, stripe, ring, depth, hier, libs, streamed, fused, engine, graph):
     prefix = str(tmp_path / "ar")
     rc, out = mpirun(np_, HIP_F32, [8, count, stripe, ring, depth, 0, 0, hier, libs, prefix], streamed=streamed,
                      fused=fused, engine=engine, graph=graph, repeat=4 if graph else 1)
