@@ -17,8 +17,9 @@ $(PROBE): tools/hbm_probe.hip
 # The library: four kernel translation units over one header of templates
 # (engine.h) -- reduce.hip, the SUM kernels, reduce_ops.hip, the MAX / MIN
 # kernels, reduce_prod.hip, the PROD and bitwise kernels, and reduce_scale.hip,
-# the scaled sums, which also takes in reduce_f8.hip, the OCP FP8 types (the
-# library keeps four code objects, the scaled sums' last), compiled side by
+# the scaled sums, which also takes in reduce_f8.hip, the OCP FP8 types, and
+# reduce_widen.hip, the widened sums (the library keeps four code objects, the
+# scaled sums' last), compiled side by
 # side (reduce.hip the longest) -- and the host files (seconds each), as
 # objects under build/obj, linked once.  The link order is the order of the
 # library's code objects: the SUM unit first, new units last.
@@ -79,7 +80,8 @@ CPP_BINS = build/plan_dump build/collectives_host build/collectives_host_f32 bui
            build/prod_add build/prod_compute_host build/prod_compute_hip build/prod_comm_host build/prod_comm_hip \
            build/scale_finish build/scale_compute_host build/scale_compute_hip \
            build/f8_add build/f8_compute_host build/f8_compute_hip \
-           build/types_comm_host build/types_comm_hip
+           build/types_comm_host build/types_comm_hip \
+           build/widen_sum build/widen_sum_hip
 
 cpp: $(CPP_BINS)
 
@@ -224,6 +226,17 @@ build/types_comm_host: tests/cpp/types_comm.cpp $(HDRS)
 	$(CXX) $(CXXFLAGS) -fopenmp -DHICCL_PORT_HOST -o $@ $< $(MPI_LINK)
 
 build/types_comm_hip: tests/cpp/types_comm.cpp $(HDRS) $(LIB)
+	@mkdir -p build
+	$(CXX) $(CXXFLAGS) $(HIP_HOST) -o $@ $< $(HIP_LINK) $(MPI_LINK)
+
+# Widened sums: HiCCL::WidenCompute<T> (bf16, f16, f8e4m3, f8e5m2 inputs, float
+# outputs) on the host port -- a stand-alone program that tests/test_widen_cpu.py
+# also builds with sanitizers -- and on the GPU (tests/test_widen_gpu.py)
+build/widen_sum: tests/cpp/widen_sum.cpp $(HDRS)
+	@mkdir -p build
+	$(CXX) $(CXXFLAGS) -fopenmp -DHICCL_PORT_HOST -o $@ $< $(MPI_LINK)
+
+build/widen_sum_hip: tests/cpp/widen_sum.cpp $(HDRS) $(LIB)
 	@mkdir -p build
 	$(CXX) $(CXXFLAGS) $(HIP_HOST) -o $@ $< $(HIP_LINK) $(MPI_LINK)
 

@@ -11,6 +11,6 @@ from ._lib import (HICCL_ACC_NATIVE, HICCL_ACC_WIDE, HICCL_BFLOAT16, HICCL_ENGIN
                    HICCL_OP_BAND, HICCL_OP_BOR, HICCL_OP_BXOR, HICCL_OP_MAX, HICCL_OP_MIN, HICCL_OP_PROD, HICCL_OP_SUM,
                    HicclError, LIB_PATH, header_functions, lib)
 from .compute import (Compute, HostPipe, Program, auto_choice, bucket, fill_uniform, reduce, reduce_ptrs,  # noqa: F401
-                      stream_copy)
+                      reduce_widened, reduce_widened_ptrs, stream_copy)
 
 __version__ = "0.3.0"

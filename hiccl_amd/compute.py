@@ -165,6 +165,89 @@ def reduce_ptrs(dtype_code, out_ptr, in_ptrs, count, stream=None, config=None, o
     L.check(rc, "hiccl_reduce")
 
 
+_WIDEN_IN = (torch.bfloat16, torch.float16) + _FP8  # inputs of a widened sum; its output is f32
+
+
+def _check_widened(in_dtype, out_dtype):
+    """The dtypes of a widened sum (hiccl_reduce_widened): bf16, f16 or FP8
+    inputs, an f32 output -- refused here, before any device work.  Torch
+    dtypes or HICCL_* codes."""
+    out_ok = out_dtype == torch.float32 if isinstance(out_dtype, torch.dtype) else int(out_dtype) == L.HICCL_FLOAT32
+    if not out_ok:
+        raise TypeError(f"hiccl: a widened sum writes torch.float32, not {out_dtype}")
+    if isinstance(in_dtype, torch.dtype):
+        in_ok = in_dtype in _WIDEN_IN
+    else:
+        in_ok = int(in_dtype) in (L.HICCL_BFLOAT16, L.HICCL_FLOAT16, L.HICCL_FLOAT8_E4M3, L.HICCL_FLOAT8_E5M2)
+    if not in_ok:
+        raise TypeError(f"hiccl: widened sums take bf16, f16, float8_e4m3fn or float8_e5m2 inputs, not {in_dtype}")
+
+
+def _check_widened_config(config):
+    if config is not None and config.get("acc", L.HICCL_ACC_NATIVE) != L.HICCL_ACC_NATIVE:
+        raise ValueError("hiccl: a widened sum always accumulates in f32: leave acc at HICCL_ACC_NATIVE")
+
+
+def reduce_widened(out, inputs, count=None, stream=None, config=None, scale=None):
+    """out[:count] = ((0.0f + float(inputs[0])) + float(inputs[1])) + ... in the
+    list order, every add an f32 add: bf16, f16 or FP8 ``inputs`` (one dtype)
+    summed into a ``torch.float32`` ``out`` in one pass (hiccl_reduce_widened)
+    -- low-precision gradient buckets into f32 master gradients.  The result is
+    :func:`reduce` in f32 on ``x.float()`` inputs, bit for bit, without the
+    converted copies.
+
+    ``scale``: the f32 sum times ``float32(scale)``, one f32 multiply at store
+    time.  ``out`` must not overlap any input (the element sizes differ, so
+    nothing runs in place).  Asynchronous on ``stream``; ``config`` as
+    :func:`reduce`'s, ``acc`` left native.  The kernels are untuned: a config
+    that names a shape they lack raises HicclError.
+    """
+    _check_tensor(out, "out")
+    if count is None:
+        count = out.numel()
+    if count < 0:
+        raise ValueError(f"hiccl: count={count} < 0")
+    inputs = list(inputs)
+    in_dtype = None
+    ptrs = []
+    for k, x in enumerate(inputs):
+        _check_tensor(x, f"inputs[{k}]")
+        if x.device != out.device:
+            raise ValueError(f"hiccl: inputs[{k}] is on {x.device}, out on {out.device}")
+        if in_dtype is None:
+            in_dtype = x.dtype
+        elif x.dtype != in_dtype:
+            raise TypeError(f"hiccl: inputs[{k}] dtype {x.dtype} != inputs[0] dtype {in_dtype}")
+        if x.numel() < count:
+            raise ValueError(f"hiccl: inputs[{k}] has {x.numel()} < count={count} elements")
+        ptrs.append(x.data_ptr())
+    if in_dtype is None:
+        raise ValueError("hiccl: reduce_widened needs at least one input to tell the input dtype "
+                         "(reduce_widened_ptrs takes it as an argument)")
+    _check_widened(in_dtype, out.dtype)
+    if out.numel() < count:
+        raise ValueError(f"hiccl: out has {out.numel()} < count={count} elements")
+    with torch.cuda.device(out.device):  # the library launches on the current device
+        reduce_widened_ptrs(L.DTYPE_OF_TORCH[in_dtype], out.data_ptr(), ptrs, count,
+                            stream=_stream_handle(stream, out.device).value or 0, config=config, scale=scale)
+    return out
+
+
+def reduce_widened_ptrs(in_dtype_code, out_ptr, in_ptrs, count, stream=None, config=None, scale=None,
+                        out_dtype_code=L.HICCL_FLOAT32):
+    """Raw-pointer form of :func:`reduce_widened` (pointers already offset)."""
+    _check_widened(in_dtype_code, out_dtype_code)
+    _check_widened_config(config)
+    alpha = None
+    if scale is not None:
+        alpha = ctypes.byref(ctypes.c_double(_check_scale(scale, in_dtype_code)))
+    tab = _ptr_table(list(in_ptrs))
+    cfg = ctypes.byref(L.ReduceConfig(**config)) if config is not None else None
+    rc = L.lib().hiccl_reduce_widened(int(in_dtype_code), int(out_dtype_code), alpha, ctypes.c_void_p(out_ptr), tab,
+                                      len(in_ptrs), count, _stream_handle(stream), cfg)
+    L.check(rc, "hiccl_reduce_widened")
+
+
 def bucket(n, count, dtype=torch.float32, device=None):
     """A reduction bucket in the library's layout (hiccl_bucket_alloc): n
     inputs and one output of ``count`` elements carved from ONE device
@@ -184,7 +267,7 @@ def bucket(n, count, dtype=torch.float32, device=None):
     return views[:n], views[n]
 
 
-def auto_choice(dtype, count, n, config=None, cus=256, op=L.HICCL_OP_SUM, scale=False):
+def auto_choice(dtype, count, n, config=None, cus=256, op=L.HICCL_OP_SUM, scale=False, out_dtype=None):
     """What a one-shot call (and a one-compute plan at TILE unroll 2 / 4 or
     AUTO) resolves to on a GPU of ``cus`` CUs, without a device:
     ``hiccl_reduce_auto_choice_ex`` (``op`` other than SUM:
@@ -192,11 +275,19 @@ def auto_choice(dtype, count, n, config=None, cus=256, op=L.HICCL_OP_SUM, scale=
     ``hiccl_reduce_auto_choice_scaled``).  ``dtype``: a torch dtype or an
     HICCL_* code; ``n`` may be a plan's packet-weighted mean.  Returns a dict
     with engine, unroll, blocks_per_cu, dynamic and store_policy (2 nt, 4
-    write-through); raises HicclError for a config no kernel has."""
+    write-through); raises HicclError for a config no kernel has.
+    ``out_dtype`` (torch.float32 with a bf16, f16 or FP8 ``dtype``): a widened
+    sum, ``hiccl_reduce_auto_choice_widened`` -- the same answer scaled or not."""
     dt = L.DTYPE_OF_TORCH[dtype] if isinstance(dtype, torch.dtype) else int(dtype)
     cfg = ctypes.byref(L.ReduceConfig(**config)) if config else None
     out = [ctypes.c_int() for _ in range(5)]
-    if scale:
+    if out_dtype is not None:
+        _check_widened(dtype if isinstance(dtype, torch.dtype) else dt, out_dtype)
+        if op != L.HICCL_OP_SUM:
+            raise ValueError("hiccl: only sums are widened: out_dtype= goes with HICCL_OP_SUM")
+        _check_widened_config(config)
+        rc = L.lib().hiccl_reduce_auto_choice_widened(dt, cfg, count, float(n), cus, *[ctypes.byref(v) for v in out])
+    elif scale:
         _check_scale(1.0, dtype if isinstance(dtype, torch.dtype) else dt, op)
         rc = L.lib().hiccl_reduce_auto_choice_scaled(dt, cfg, count, float(n), cus, *[ctypes.byref(v) for v in out])
     elif op != L.HICCL_OP_SUM:
@@ -223,11 +314,20 @@ class Compute:
     """
 
     def __init__(self, dtype=torch.float32, device=None, myid=0, acc=L.HICCL_ACC_NATIVE,
-                 engine=L.HICCL_ENGINE_AUTO, config=None, op=L.HICCL_OP_SUM, scale=None):
+                 engine=L.HICCL_ENGINE_AUTO, config=None, op=L.HICCL_OP_SUM, scale=None, out_dtype=None):
         self.dtype = dtype
         self.code = L.DTYPE_OF_TORCH[dtype]
         if scale is not None:
             scale = _check_scale(scale, dtype, op)
+        # a widened plan (hiccl_reduce_plan_set_out_dtype): `dtype` inputs, f32 outputs
+        self.out_dtype = dtype if out_dtype is None else out_dtype
+        if out_dtype is not None:
+            _check_widened(dtype, out_dtype)
+            if op != L.HICCL_OP_SUM:
+                raise ValueError("hiccl: only sums are widened: out_dtype= goes with HICCL_OP_SUM")
+            if acc != L.HICCL_ACC_NATIVE:
+                raise ValueError("hiccl: a widened sum always accumulates in f32: leave acc at HICCL_ACC_NATIVE")
+            _check_widened_config(config)
         if device is None:
             device = torch.cuda.current_device()
         self.device = device
@@ -248,6 +348,9 @@ class Compute:
             self.set_config(config)
         if op != L.HICCL_OP_SUM:
             self.set_op(op)
+        if out_dtype is not None:
+            L.check(L.lib().hiccl_reduce_plan_set_out_dtype(self._plan, L.DTYPE_OF_TORCH[out_dtype]),
+                    "plan_set_out_dtype")
         if scale is not None:
             self.set_scale(scale)
 
@@ -327,7 +430,7 @@ class Compute:
             return
         esz = L.lib().hiccl_dtype_size(self.code)
         ins = [self._ptr(b, esz) for b in inputbuf]
-        ot, op = self._ptr(outputbuf, esz)
+        ot, op = self._ptr(outputbuf, L.lib().hiccl_dtype_size(L.DTYPE_OF_TORCH[self.out_dtype]))
         tab = _ptr_table([p for _, p in ins])
         L.check(L.lib().hiccl_reduce_plan_add(self._plan, ctypes.c_void_p(op), tab, len(ins), count),
                 "plan_add")
@@ -367,7 +470,8 @@ class Compute:
         L.check(L.lib().hiccl_reduce_plan_sync(self._plan), "plan_sync")
 
     def bytes(self):
-        """Sum of count * (n + 1) * sizeof(T) (compute.h:197-203)."""
+        """Sum of count * (n + 1) * sizeof(T) (compute.h:197-203); a widened
+        plan: count * (n * sizeof(T) + 4)."""
         return L.lib().hiccl_reduce_plan_bytes(self._plan)
 
     def report(self):

@@ -6,8 +6,9 @@
 // by side in the build: reduce.hip instantiates the tables for the SUM ops
 // (kPartSum), reduce_ops.hip for the MAX / MIN ops (kPartMaxMin),
 // reduce_prod.hip for PROD and the bitwise ops (kPartProd),
-// reduce_scale.hip for the post-scaled sums (kPartScale) and reduce_f8.hip
-// for every op of the two OCP FP8 types (kPartF8).  All
+// reduce_scale.hip for the post-scaled sums (kPartScale), reduce_f8.hip
+// for every op of the two OCP FP8 types (kPartF8) and reduce_widen.hip for the
+// widened sums (kPartWiden; the last two are included from reduce_scale.hip).  All
 // take their ops from the one list below (with_elem<PART>), so a type or an
 // operator is still added in one place.  Everything here is in an anonymous
 // namespace: a kernel belongs to the unit that instantiates it.
@@ -57,6 +58,22 @@ template <int POL>
 __device__ __forceinline__ u32x4 load_pkt(rsrc_t r, uint32_t voff) {
   constexpr int lp = POL % 10;
   return __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, 0, lp == 1 ? 2 : lp == kPolLoadSys ? 17 : 0);
+}
+
+// The narrow input packets of the widened sums (four elements: 8 B of a
+// 2-byte type, 4 B of FP8), under the same load policies.
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+
+template <int POL>
+__device__ __forceinline__ u32x2 load_pkt_b64(rsrc_t r, uint32_t voff) {
+  constexpr int lp = POL % 10;
+  return __builtin_amdgcn_raw_buffer_load_b64(r, (int)voff, 0, lp == 1 ? 2 : lp == kPolLoadSys ? 17 : 0);
+}
+
+template <int POL>
+__device__ __forceinline__ uint32_t load_pkt_b32(rsrc_t r, uint32_t voff) {
+  constexpr int lp = POL % 10;
+  return __builtin_amdgcn_raw_buffer_load_b32(r, (int)voff, 0, lp == 1 ? 2 : lp == kPolLoadSys ? 17 : 0);
 }
 
 template <int POL>
@@ -819,6 +836,113 @@ struct OpF8Scaled : Base {
   }
 };
 
+// ------------------------------------------------------------ widened sums --
+// bf16, f16 or FP8 inputs summed into an f32 OUTPUT (hiccl_reduce_widened): the
+// arithmetic of the f32-accumulating ops above -- widen (exact), one f32 add per
+// input in list order from +0 -- whose accumulator is stored as it is instead of
+// being rounded back.  The one op family with two element sizes: kEsz is the
+// inputs', kOutEsz the output's, and a packet is FOUR elements -- 16 B of the
+// output (one f32x4 accumulator, one buffer_store_dwordx4) and 4 * kEsz bytes
+// of every input (in_t: one buffer_load_dwordx2 of a 2-byte type, one
+// buffer_load_dword of FP8).  Every byte quantity the engines pass along is the
+// output's; the inputs' are those times kEsz / kOutEsz (in_bytes).
+// There is one kernel for the plain and the scaled form: the store multiplies
+// by a32, and the plain form passes 1.0f (fl32(s * 1.0f) is s for every s that
+// is not a NaN, and NaNs compare by NaN-ness).
+// An op of this family is told by kOutEsz, which no other op has.
+template <class Op, class = void>
+struct widens_out : std::false_type {};
+template <class Op>
+struct widens_out<Op, std::enable_if_t<(Op::kOutEsz > 0)>> : std::true_type {};
+
+// bytes per output element, and an input's byte quantity from the output's
+template <class Op>
+constexpr int out_esz() {
+  if constexpr (widens_out<Op>::value) return Op::kOutEsz;
+  else return Op::kEsz;
+}
+template <class Op, class V>
+__device__ __forceinline__ V in_bytes(V out_bytes) {
+  if constexpr (widens_out<Op>::value) return out_bytes / (V)(Op::kOutEsz / Op::kEsz);
+  else return out_bytes;
+}
+
+// what one lane loads of one input per packet
+template <class Op, class = void>
+struct in_pkt {
+  typedef u32x4 type;
+};
+template <class Op>
+struct in_pkt<Op, std::void_t<typename Op::in_t>> {
+  typedef typename Op::in_t type;
+};
+template <class Op> using in_pkt_t = typename in_pkt<Op>::type;
+
+template <class Op, int POL>
+__device__ __forceinline__ in_pkt_t<Op> load_in(rsrc_t r, uint32_t voff) {
+  if constexpr (widens_out<Op>::value) return Op::template load<POL>(r, in_bytes<Op>(voff));
+  else return load_pkt<POL>(r, voff);
+}
+
+// The widening of one input packet (W of OpWiden): four elements -> f32x4.
+struct WidenBF16 {
+  static constexpr int kEsz = 2;
+  typedef u32x2 in_t;
+  template <int POL>
+  __device__ static in_t load(rsrc_t r, uint32_t voff) { return load_pkt_b64<POL>(r, voff); }
+  __device__ static f32x4 widen4(in_t p) { return f32x4{bf_lo(p[0]), bf_hi(p[0]), bf_lo(p[1]), bf_hi(p[1])}; }
+  __device__ static float ld(const char *p) { return __uint_as_float((uint32_t)(gld<uint16_t>(p)) << 16); }
+};
+
+struct WidenF16 {
+  static constexpr int kEsz = 2;
+  typedef u32x2 in_t;
+  template <int POL>
+  __device__ static in_t load(rsrc_t r, uint32_t voff) { return load_pkt_b64<POL>(r, voff); }
+  __device__ static f32x4 widen4(in_t p) {
+    return f32x4{f16_widen(p[0], 0), f16_widen(p[0], 1), f16_widen(p[1], 0), f16_widen(p[1], 1)};
+  }
+  __device__ static float ld(const char *p) { return (float)f16_ld(p); }
+};
+
+template <int FMT>
+struct WidenF8 {
+  static constexpr int kEsz = 1;
+  typedef uint32_t in_t;
+  template <int POL>
+  __device__ static in_t load(rsrc_t r, uint32_t voff) { return load_pkt_b32<POL>(r, voff); }
+  __device__ static f32x4 widen4(in_t p) {
+    float v[4];
+    f8_widen4<FMT>(p, v);
+    return f32x4{v[0], v[1], v[2], v[3]};
+  }
+  __device__ static float ld(const char *p) { return F8<FMT>::ld(p); }
+};
+
+template <class W>
+struct OpWiden {
+  static constexpr bool kWidens = true;
+  static constexpr int kEsz = W::kEsz;
+  static constexpr int kOutEsz = 4;
+  typedef typename W::in_t in_t;
+  template <int POL>
+  __device__ static in_t load(rsrc_t r, uint32_t voff) { return W::template load<POL>(r, voff); }
+  typedef f32x4 acc_t;
+  __device__ static acc_t zero() { return (f32x4)(0.0f); }
+  __device__ static acc_t add(acc_t a, in_t p) { return a + W::widen4(p); }
+  typedef float fin_t;
+  __device__ static float fin(const Scale &s) { return s.a32; }
+  __device__ static u32x4 pack(acc_t a, float a32) { return __builtin_bit_cast(u32x4, a * a32); }
+  typedef float sacc_t;
+  __device__ static sacc_t szero() { return 0.0f; }
+  __device__ static sacc_t sadd(sacc_t a, const char *p) { return a + W::ld(p); }
+  __device__ static void sstore(char *p, float a, float a32) { gst<float>(p, a * a32); }
+};
+
+typedef OpWiden<WidenBF16> OpBF16ToF32;
+typedef OpWiden<WidenF16> OpF16ToF32;
+template <int FMT> using OpF8ToF32 = OpWiden<WidenF8<FMT>>;
+
 // ----------------------------------------------------------- tile engine --
 //
 // A compute is split as [head scalars | npkt 16-B packets | tail scalars],
@@ -841,14 +965,15 @@ struct ArgInputs {
 template <class Op, int POL = 11, class Inputs>
 __device__ __forceinline__ void scalar_part(char *out, Inputs in, uint32_t n, uint32_t head,
                                             uint64_t npkt, uint32_t tail, int tid, fin_t<Op> fin = {}) {
-  constexpr int V = kPacket / Op::kEsz;
+  constexpr int V = kPacket / out_esz<Op>();
   if (tid >= (int)(head + tail)) return;
   if constexpr (POL % 10 == kPolLoadSys) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
   uint64_t e = (tid < (int)head) ? (uint64_t)tid : (uint64_t)head + npkt * V + (tid - head);
   uint64_t off = e * Op::kEsz;
   typename Op::sacc_t acc = Op::szero();
   for (uint32_t k = 0; k < n; k++) acc = Op::sadd(acc, in(k) + off);
-  sstore_fin<Op>(out + off, acc, fin);
+  if constexpr (widens_out<Op>::value) sstore_fin<Op>(out + e * Op::kOutEsz, acc, fin);
+  else sstore_fin<Op>(out + off, acc, fin);
   if constexpr (POL / 10 == kPolStoreSys) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
 }
 
@@ -874,8 +999,8 @@ __device__ __forceinline__ void group_at(typename Op::acc_t (&acc)[U], Inputs in
                                          const uint32_t (&voff)[U]) {
   rsrc_t r[G];
 #pragma unroll
-  for (int j = 0; j < G; j++) r[j] = make_rsrc(in(g + j) + tile_off, tile_bytes);
-  u32x4 x[G][U];
+  for (int j = 0; j < G; j++) r[j] = make_rsrc(in(g + j) + in_bytes<Op>(tile_off), in_bytes<Op>(tile_bytes));
+  in_pkt_t<Op> x[G][U];
   // Every load of the group is issued before the first add, input by input
   // (the barriers pin that order, so the adds -- input 0 first -- wait with
   // a vmcnt staircase instead of one vmcnt(0)).  Without them the scheduler
@@ -885,7 +1010,7 @@ __device__ __forceinline__ void group_at(typename Op::acc_t (&acc)[U], Inputs in
 #pragma unroll
   for (int j = 0; j < G; j++) {
 #pragma unroll
-    for (int u = 0; u < U; u++) x[j][u] = load_pkt<POL>(r[j], voff[u]);
+    for (int u = 0; u < U; u++) x[j][u] = load_in<Op, POL>(r[j], voff[u]);
     __builtin_amdgcn_sched_barrier(0);
     if constexpr (PACED) {
       if (j + 1 < G) {
@@ -998,17 +1123,19 @@ __device__ __forceinline__ void chunk_body(char *outb, Inputs in, uint32_t n, ui
 #pragma unroll
   for (int p = 0; p < P; p++) acc[p] = Op::zero();
   if (n > 0) {
-    u32x4 x[P], y[P];
+    in_pkt_t<Op> x[P], y[P];
+    const uint64_t ioff = in_bytes<Op>(off);
+    const uint32_t ibytes = in_bytes<Op>(nbytes);
     {
-      rsrc_t r = make_rsrc(in(0) + off, nbytes);
+      rsrc_t r = make_rsrc(in(0) + ioff, ibytes);
 #pragma unroll
-      for (int p = 0; p < P; p++) x[p] = load_pkt<POL>(r, voff[p]);
+      for (int p = 0; p < P; p++) x[p] = load_in<Op, POL>(r, voff[p]);
     }
     uint32_t j = 0;
     for (; j + 2 <= n; j += 2) {  // x: input j in flight
-      rsrc_t ry = make_rsrc(in(j + 1) + off, nbytes);
+      rsrc_t ry = make_rsrc(in(j + 1) + ioff, ibytes);
 #pragma unroll
-      for (int p = 0; p < P; p++) y[p] = load_pkt<POL>(ry, voff[p]);
+      for (int p = 0; p < P; p++) y[p] = load_in<Op, POL>(ry, voff[p]);
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int p = 0; p < P; p++) {
@@ -1018,9 +1145,9 @@ __device__ __forceinline__ void chunk_body(char *outb, Inputs in, uint32_t n, ui
       }
       __builtin_amdgcn_sched_barrier(0);
       const bool more = j + 2 < n;
-      rsrc_t rx = make_rsrc(in(more ? j + 2 : j + 1) + off, more ? nbytes : 0u);
+      rsrc_t rx = make_rsrc(in(more ? j + 2 : j + 1) + ioff, more ? ibytes : 0u);
 #pragma unroll
-      for (int p = 0; p < P; p++) x[p] = load_pkt<POL>(rx, voff[p]);
+      for (int p = 0; p < P; p++) x[p] = load_in<Op, POL>(rx, voff[p]);
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int p = 0; p < P; p++) {
@@ -1197,7 +1324,7 @@ __device__ __forceinline__ void single_kernel(const SingleArgs &a, fin_t<Op> fin
   if (a.npkt == 0) return;  // (the host never passes a sched counter then)
   const uint64_t shift = (uint64_t)a.head * Op::kEsz;
   Shifted<ArgInputs> in{raw, shift};
-  char *outb = a.out + shift;
+  char *outb = a.out + (uint64_t)a.head * out_esz<Op>();
   constexpr uint64_t TILE = (uint64_t)BLOCK * U;
   for_each_unit(a.sched, a.grab, 0, a.ntiles, [&](uint64_t u, auto hook) {
     const uint64_t t = tile_order(u, a.ntiles, a.order);
@@ -1307,7 +1434,8 @@ __global__ __launch_bounds__(BLOCK) void k_reduce_plan_scaled(PlanArgsScaled a) 
     Shifted<TableInputs> in{raw, shift};
     const uint64_t left = d.npkt - pkt0;
     const uint32_t tile_bytes = (uint32_t)((left < TILE ? left : TILE) * kPacket);
-    unit_body<Op, U, POL, ENG>(d.out + shift, in, d.n, pkt0 * kPacket, tile_bytes, voff, hook, fin);
+    unit_body<Op, U, POL, ENG>(d.out + (uint64_t)d.head * out_esz<Op>(), in, d.n, pkt0 * kPacket, tile_bytes, voff, hook,
+                               fin);
   });
 }
 
@@ -1520,6 +1648,7 @@ constexpr int kPartMaxMin = 1;
 constexpr int kPartProd = 2;  // PROD, BAND, BOR, BXOR
 constexpr int kPartScale = 3;  // post-scaled sums (kOpScaledSum)
 constexpr int kPartF8 = 4;  // the OCP FP8 types, every operator they have
+constexpr int kPartWiden = 5;  // widened sums (kOpWidenSum): 2-byte and FP8 inputs, f32 output
 
 // MAX and MIN of the six arithmetic types; HICCL_BYTES has no operator.
 template <bool MAX, class R, class F>
@@ -1621,9 +1750,26 @@ R with_elem_f8(int dtype, int acc, int op, R unknown, F f) {
   }
 }
 
+// Widened sums: the dtype is the INPUTS' (the output is f32), the accumulator
+// is the op's own (acc must be native: the host refuses HICCL_ACC_WIDE).
+// Untuned, and FP8 inputs come here too, not to kPartF8.
+template <class R, class F>
+R with_elem_widen(int dtype, int acc, R unknown, F f) {
+  if (acc != HICCL_ACC_NATIVE) return unknown;
+  switch (dtype) {
+    case HICCL_BFLOAT16: return f(Elem<HICCL_BFLOAT16, OpBF16ToF32, false>());
+    case HICCL_FLOAT16: return f(Elem<HICCL_FLOAT16, OpF16ToF32, false>());
+    case HICCL_FLOAT8_E4M3: return f(Elem<HICCL_FLOAT8_E4M3, OpF8ToF32<kE4M3>, false>());
+    case HICCL_FLOAT8_E5M2: return f(Elem<HICCL_FLOAT8_E5M2, OpF8ToF32<kE5M2>, false>());
+    default: return unknown;
+  }
+}
+
 template <int PART, class R, class F>
 R with_elem(int dtype, int acc, int op, R unknown, F f) {
-  if constexpr (PART == kPartF8) {
+  if constexpr (PART == kPartWiden) {
+    return op == kOpWidenSum ? with_elem_widen(dtype, acc, unknown, f) : unknown;
+  } else if constexpr (PART == kPartF8) {
     return with_elem_f8(dtype, acc, op, unknown, f);
   } else if constexpr (PART == kPartScale) {
     return op == kOpScaledSum ? with_elem_scale(dtype, acc, unknown, f) : unknown;

@@ -44,6 +44,12 @@ constexpr int kMaxArgInputs = 64;  // kernarg pointer table (512 B)
 // through the policy and the kernel tables as an operator of its own, which is
 // no hiccl_op_t value: the public entries never take it (known_op refuses it).
 constexpr int kOpScaledSum = 0x100;
+// A widened sum (hiccl_reduce_widened, hiccl_reduce_plan_set_out_dtype: bf16,
+// f16 or FP8 inputs, f32 output) likewise.  The dtype that travels with it is
+// the INPUTS'; every packet count is in packets of the f32 OUTPUT (four
+// elements).  Its kernels are the scaled ones' kind (they take a Scale): an
+// unscaled widened sum passes alpha = 1.
+constexpr int kOpWidenSum = 0x101;
 
 // The scale of a scaled sum: alpha as the caller gave it (f64 kernels) and
 // rounded to nearest even to f32 (every other type).  The scaled kernels take
@@ -186,6 +192,9 @@ plan_fn pick_plan_scale(int dtype, int acc, int op, int engine, int unroll, int 
 single_fn pick_single_f8(int dtype, int acc, int op, int engine, int block, int unroll, int pol);
 plan_fn pick_plan_f8(int dtype, int acc, int op, int engine, int unroll, int pol);
 prog_fn pick_prog_f8(int dtype, int op, int unroll);
+// the widened sums (reduce_widen.hip; op == kOpWidenSum, dtype: the inputs'): no program kernels
+single_fn pick_single_widen(int dtype, int acc, int op, int engine, int block, int unroll, int pol);
+plan_fn pick_plan_widen(int dtype, int acc, int op, int engine, int unroll, int pol);
 
 // ---- the plain kernels
 

@@ -24,7 +24,7 @@ uint32_t log2u(int v) {
 int reduce_via_table(int dtype, const Cfg &c, const Scale &scale, void *out, const void *const *in, int n,
                      size_t count, hipStream_t s) {
   DescTable t((size_t)n, unit_pkts(c.engine, dtype, c.acc, c.unroll));
-  t.add(out, in, (size_t)n, count, esize(dtype));
+  t.add(out, in, (size_t)n, count, out_esize(dtype, c.op));
   const std::vector<char> host = t.image();
   char *dmem = nullptr;
   if (int e = check_hip(hipMallocAsync((void **)&dmem, host.size(), s), "hiccl_reduce: hipMallocAsync")) return e;
@@ -70,15 +70,42 @@ int check_scale(int dtype, double alpha, const std::string &who, Scale *scale) {
   return 0;
 }
 
-// hiccl_reduce_op (scale NULL: `op` is a hiccl_op_t the caller has checked) and
-// hiccl_reduce_scaled (op == kOpScaledSum).
+bool widen_in_dtype(int dtype) {
+  return dtype == HICCL_BFLOAT16 || dtype == HICCL_FLOAT16 || dtype == HICCL_FLOAT8_E4M3 || dtype == HICCL_FLOAT8_E5M2;
+}
+
+int check_widened(int in_dtype, int out_dtype, int acc, const double *alpha, const std::string &who, Scale *scale) {
+  if (out_dtype != HICCL_FLOAT32)
+    return fail(hipErrorInvalidValue, who + ": a widened sum writes HICCL_FLOAT32 only (out_dtype " +
+                                          std::to_string(out_dtype) + ")");
+  if (!widen_in_dtype(in_dtype))
+    return fail(hipErrorInvalidValue, who + ": widened sums take HICCL_BFLOAT16, HICCL_FLOAT16, HICCL_FLOAT8_E4M3 or "
+                                            "HICCL_FLOAT8_E5M2 inputs (in_dtype " + std::to_string(in_dtype) + ")");
+  if (acc != HICCL_ACC_NATIVE)
+    return fail(hipErrorInvalidValue, who + ": a widened sum always accumulates in f32: leave acc at HICCL_ACC_NATIVE");
+  Scale sc{1.0, 1.0f, 0u};  // unscaled: the kernels multiply by one
+  if (alpha)
+    if (int e = check_scale(in_dtype, *alpha, who, &sc)) return e;
+  if (scale) *scale = sc;
+  return 0;
+}
+
+// hiccl_reduce_op (scale NULL: `op` is a hiccl_op_t the caller has checked),
+// hiccl_reduce_scaled (op == kOpScaledSum) and hiccl_reduce_widened (op ==
+// kOpWidenSum: `dtype` is the inputs', the output is f32).
 int reduce_call(int dtype, int op, const Scale *scale, void *out, const void *const *in, int n, size_t count,
                 void *stream, const hiccl_reduce_config_t *cfg) {
-  const size_t esz = esize(dtype);
+  const bool widened = op == kOpWidenSum;
+  const size_t esz = out_esize(dtype, op);  // of the OUTPUT: the split, the packets and the bytes written are its
   const Scale sc = scale ? *scale : Scale{0.0, 0.0f, 0u};
+  if (widened) {
+    if (int e = check_buffers_widened(out, in, n, count, esize(dtype), esz)) return e;
+  }
   if (count == 0) return 0;
   if (dtype == HICCL_BYTES && n != 1) return fail(hipErrorInvalidValue, "hiccl_reduce: HICCL_BYTES copies need n == 1");
-  if (int e = check_buffers(out, in, n, count, esz)) return e;
+  if (!widened) {
+    if (int e = check_buffers(out, in, n, count, esz)) return e;
+  }
   if (int e = check_cfg(cfg, "hiccl_reduce")) return e;
   hipStream_t s = (hipStream_t)stream;
   const int dev = current_device();
@@ -135,7 +162,7 @@ namespace {
 // hiccl_reduce_auto_choice_op and _scaled, the operator checked by the caller.
 int auto_choice(int dtype, int op, const hiccl_reduce_config_t *cfg, size_t count, double n, int cus, int *engine,
                 int *unroll, int *blocks_per_cu, int *dynamic, int *store_policy) {
-  const size_t esz = esize(dtype);
+  const size_t esz = out_esize(dtype, op);
   if (cus <= 0 || n < 0) return fail(hipErrorInvalidValue, "auto_choice: cus must be > 0 and n >= 0");
   if (int e = check_cfg(cfg, "auto_choice")) return e;
   CusOverride scoped(cus);  // no device query: the choice for `cus` CUs
@@ -170,6 +197,22 @@ int hiccl_reduce_scaled(int dtype, double alpha, void *out, const void *const *i
   Scale sc;
   if (int e = check_scale(dtype, alpha, "hiccl_reduce_scaled", &sc)) return e;
   return reduce_call(dtype, kOpScaledSum, &sc, out, in, n, count, stream, cfg);
+}
+
+int hiccl_reduce_widened(int in_dtype, int out_dtype, const double *alpha, void *out, const void *const *in, int n,
+                         size_t count, void *stream, const hiccl_reduce_config_t *cfg) {
+  Scale sc;
+  if (int e = check_widened(in_dtype, out_dtype, cfg ? cfg->acc : HICCL_ACC_NATIVE, alpha, "hiccl_reduce_widened", &sc))
+    return e;
+  return reduce_call(in_dtype, kOpWidenSum, &sc, out, in, n, count, stream, cfg);
+}
+
+int hiccl_reduce_auto_choice_widened(int in_dtype, const hiccl_reduce_config_t *cfg, size_t count, double n, int cus,
+                                     int *engine, int *unroll, int *blocks_per_cu, int *dynamic, int *store_policy) {
+  if (int e = check_widened(in_dtype, HICCL_FLOAT32, cfg ? cfg->acc : HICCL_ACC_NATIVE, nullptr, "auto_choice_widened",
+                            nullptr))
+    return e;
+  return auto_choice(in_dtype, kOpWidenSum, cfg, count, n, cus, engine, unroll, blocks_per_cu, dynamic, store_policy);
 }
 
 int hiccl_reduce_ex(int dtype, void *out, const void *const *in, int n, size_t count,

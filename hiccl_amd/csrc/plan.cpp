@@ -67,10 +67,10 @@ static int plan_store_peer(const hiccl_reduce_plan *p) {
   uint64_t out = 0;
   double weighted_n = 0;
   for (auto &c : p->comps) {
-    out += (uint64_t)c.count * p->esz;
+    out += (uint64_t)c.count * p->osz;  // the bytes WRITTEN
     weighted_n += (double)c.count * (double)c.in.size();
   }
-  const double n = out ? weighted_n * (double)p->esz / (double)out : 0.0;
+  const double n = out ? weighted_n * (double)p->osz / (double)out : 0.0;
   return wt_by_size(resolve(&p->req), p->dtype, n, out) ? HICCL_PEER_STORES : 0;
 }
 
@@ -115,7 +115,7 @@ int plan_upload(hiccl_reduce_plan *p, hipStream_t s) {
   double weighted_n = 0;
   size_t maxn = 0;
   for (auto &c : p->comps) {
-    const uint64_t k = split_on(c.out, c.count, p->esz).npkt;
+    const uint64_t k = split_on(c.out, c.count, p->osz).npkt;
     total_pkt += k;
     weighted_n += (double)k * c.in.size();
     if (c.in.size() > maxn) maxn = c.in.size();
@@ -127,7 +127,7 @@ int plan_upload(hiccl_reduce_plan *p, hipStream_t s) {
   p->unroll = c.unroll;
   p->bpc = c.bpc;
   DescTable t(maxn, unit_pkts(p->engine, p->dtype, c.acc, p->unroll));
-  for (auto &cp : p->comps) t.add(cp.out, cp.in.data(), cp.in.size(), cp.count, p->esz);
+  for (auto &cp : p->comps) t.add(cp.out, cp.in.data(), cp.in.size(), cp.count, p->osz);
   const std::vector<char> host = t.image();
   if (int e = check_hip(hipMalloc((void **)&p->d_block, host.size()), "plan: hipMalloc")) return e;
   if (int e = check_hip(hipMemcpy(p->d_block, host.data(), host.size(), hipMemcpyHostToDevice), "plan: upload"))
@@ -149,7 +149,7 @@ int plan_kernel(hiccl_reduce_plan *p, hipStream_t s) {
   c.bpc = p->bpc;
   PlanArgsScaled a;  // the plan itself is only read (hiccl_reduce_plan_enqueue from several threads)
   (PlanArgs &)a = p->args;
-  a.scale = p->scale;
+  a.scale = p->kernel_scale();
   return launch_plan(a, p->dtype, c, p->mean_n, p->device, s, plan_pol(p->eff_peer));
 }
 
@@ -169,13 +169,16 @@ int plan_set_field(hiccl_reduce_plan_t *p, int hiccl_reduce_config_t::*field, in
   c.*field = value;
   if (int e = check_cfg(&c, who)) return e;
   if (int e = check_op(p->dtype, c.acc, p->op, who)) return e;
+  if (p->widened && c.acc != HICCL_ACC_NATIVE)
+    return fail(hipErrorInvalidValue, std::string(who) + ": a widened plan always accumulates in f32: leave acc at "
+                                                         "HICCL_ACC_NATIVE");
   p->req = c;
   p->dirty = true;  // (the auto engine's chunk size depends on the accumulator, too)
   return 0;
 }
 
 // Does every engine config `c` may resolve to have a plan kernel of operator
-// `op` (a hiccl_op_t or kOpScaledSum) in the shape `c` names?  Empty string if
+// `op` (a hiccl_op_t, kOpScaledSum or kOpWidenSum) in the shape `c` names?  Empty string if
 // so, else why not.  No device work.
 std::string plan_config_error(const hiccl_reduce_plan *p, const hiccl_reduce_config_t &c, int op) {
   Cfg r = resolve(&c);
@@ -212,6 +215,7 @@ int hiccl_reduce_plan_create(hiccl_reduce_plan_t **plan, int dtype, int device) 
   p->dtype = dtype;
   p->device = device;
   p->esz = esize(dtype);
+  p->osz = p->esz;
   // the plan's own stream is created on first request (hiccl_reduce_plan_stream):
   // callers that launch on a shared stream never pay for one
   *plan = p;
@@ -227,6 +231,8 @@ int hiccl_reduce_plan_set_op(hiccl_reduce_plan_t *p, int op) {
   if (int e = check_op(p->dtype, p->req.acc, op, "plan_set_op")) return e;
   if (p->scaled && op != HICCL_OP_SUM)
     return fail(hipErrorInvalidValue, "plan_set_op: a scaled plan sums (HICCL_OP_SUM only): clear the scale first");
+  if (p->widened && op != HICCL_OP_SUM)
+    return fail(hipErrorInvalidValue, "plan_set_op: a widened plan sums (HICCL_OP_SUM only)");
   p->op = op;
   p->dirty = true;  // (AUTO's shape depends on the operator: MAX and MIN are untuned)
   return 0;
@@ -243,13 +249,14 @@ int hiccl_reduce_plan_set_scale(hiccl_reduce_plan_t *p, const double *alpha) {
       return fail(hipErrorInvalidValue, "plan_set_scale: only sums are scaled (the plan's op is not HICCL_OP_SUM)");
     // the scaled kernels are untuned: a config that names a shape only the
     // tuned sums have (TILE unroll 1, 2, 8, 16) is refused here, not at launch
-    const std::string why = plan_config_error(p, p->req, kOpScaledSum);
+    const std::string why = plan_config_error(p, p->req, p->widened ? kOpWidenSum : kOpScaledSum);
     if (!why.empty())
       return fail(hipErrorInvalidValue, "plan_set_scale: the plan's config names a shape the scaled kernels lack: " + why);
   }
   // a scaled sum is another kernel, untuned: AUTO's shape may differ.  A new
-  // alpha alone travels in the kernel arguments and needs no upload.
-  if (p->scaled != (alpha != nullptr)) p->dirty = true;
+  // alpha alone travels in the kernel arguments and needs no upload (nor does
+  // the scale of a widened plan, whose kernel is the same with and without).
+  if (p->scaled != (alpha != nullptr) && !p->widened) p->dirty = true;
   p->scaled = alpha != nullptr;
   p->scale = sc;
   return 0;
@@ -259,6 +266,29 @@ int hiccl_reduce_plan_scale(const hiccl_reduce_plan_t *p, double *alpha) {
   if (!p) return -1;
   if (p->scaled && alpha) *alpha = p->scale.a64;
   return p->scaled ? 1 : 0;
+}
+
+int hiccl_reduce_plan_set_out_dtype(hiccl_reduce_plan_t *p, int out_dtype) {
+  if (!p) return fail(hipErrorInvalidValue, "plan_set_out_dtype: plan is NULL");
+  if (!p->comps.empty())
+    return fail(hipErrorInvalidValue, "plan_set_out_dtype: the output dtype is set before the first add (the plan holds " +
+                                          std::to_string(p->comps.size()) + " computes)");
+  if (int e = check_widened(p->dtype, out_dtype, p->req.acc, nullptr, "plan_set_out_dtype", nullptr)) return e;
+  if (p->op != HICCL_OP_SUM)
+    return fail(hipErrorInvalidValue, "plan_set_out_dtype: only sums are widened (the plan's op is not HICCL_OP_SUM)");
+  // the widened kernels are untuned: a config that names a shape only the
+  // tuned sums have is refused here, not at launch
+  const std::string why = plan_config_error(p, p->req, kOpWidenSum);
+  if (!why.empty())
+    return fail(hipErrorInvalidValue, "plan_set_out_dtype: the plan's config names a shape the widened kernels lack: " + why);
+  p->widened = true;
+  p->osz = esize(out_dtype);
+  p->dirty = true;
+  return 0;
+}
+
+int hiccl_reduce_plan_out_dtype(const hiccl_reduce_plan_t *p) {
+  return !p ? -1 : p->widened ? (int)HICCL_FLOAT32 : p->dtype;
 }
 
 int hiccl_reduce_plan_set_engine(hiccl_reduce_plan_t *p, int engine) {
@@ -288,6 +318,9 @@ int hiccl_reduce_plan_set_config(hiccl_reduce_plan_t *p, const hiccl_reduce_conf
   const hiccl_reduce_config_t &c = cfg ? *cfg : z;
   if (int e = check_cfg(&c, "plan_set_config")) return e;
   if (int e = check_op(p->dtype, c.acc, p->op, "plan_set_config")) return e;
+  if (p->widened && c.acc != HICCL_ACC_NATIVE)
+    return fail(hipErrorInvalidValue, "plan_set_config: a widened plan always accumulates in f32: leave acc at "
+                                      "HICCL_ACC_NATIVE");
   // the shape must be one the plan kernels have, whatever engine AUTO picks
   const std::string why = plan_config_error(p, c, p->kernel_op());
   if (!why.empty()) return fail(hipErrorInvalidValue, "plan_set_config: " + why);
@@ -302,7 +335,11 @@ int hiccl_reduce_plan_add(hiccl_reduce_plan_t *p, void *out, const void *const *
                           size_t count) {
   if (!p) return fail(hipErrorInvalidValue, "plan_add: plan is NULL");
   if (p->dtype == HICCL_BYTES && n != 1) return fail(hipErrorInvalidValue, "plan_add: HICCL_BYTES copies need n == 1");
-  if (int e = check_buffers(out, in, n, count, p->esz)) return e;
+  if (p->widened) {
+    if (int e = check_buffers_widened(out, in, n, count, p->esz, p->osz)) return e;
+  } else if (int e = check_buffers(out, in, n, count, p->esz)) {
+    return e;
+  }
   if (count == 0) return 0;
   hiccl_reduce_plan::Comp c;
   c.out = out;
@@ -344,10 +381,12 @@ int hiccl_reduce_plan_launch_each(hiccl_reduce_plan_t *p, void *stream) {
   if (p->comps.empty()) return 0;
   // One one-shot launch per compute, each with the engine AUTO picks for that
   // compute alone (the reference's structure, compute.h:88-91).
-  for (auto &c : p->comps)
-    if (int e = reduce_call(p->dtype, p->kernel_op(), p->scaled ? &p->scale : nullptr, c.out, c.in.data(),
+  const Scale sc = p->kernel_scale();
+  for (auto &c : p->comps) {
+    if (int e = reduce_call(p->dtype, p->kernel_op(), p->has_scale() ? &sc : nullptr, c.out, c.in.data(),
                             (int)c.in.size(), c.count, stream, &p->req))
       return e;
+  }
   p->launched = true;
   p->last = (hipStream_t)stream;
   return 0;
@@ -381,7 +420,7 @@ void *hiccl_reduce_plan_stream(hiccl_reduce_plan_t *p) {
 size_t hiccl_reduce_plan_bytes(const hiccl_reduce_plan_t *p) {
   if (!p) return 0;
   size_t b = 0;
-  for (auto &c : p->comps) b += c.count * (c.in.size() + 1) * p->esz;
+  for (auto &c : p->comps) b += c.count * (c.in.size() * p->esz + p->osz);
   return b;
 }
 

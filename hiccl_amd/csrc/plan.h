@@ -14,8 +14,12 @@ struct hiccl_reduce_plan {
   int op = HICCL_OP_SUM;          // hiccl_reduce_plan_set_op
   bool scaled = false;            // hiccl_reduce_plan_set_scale: out = alpha * sum (op stays SUM)
   hiccl_impl::Scale scale{0.0, 0.0f, 0u};
+  bool widened = false;           // hiccl_reduce_plan_set_out_dtype: dtype inputs, f32 outputs (op stays SUM)
   // the operator the policy and the kernel tables see
-  int kernel_op() const { return scaled ? hiccl_impl::kOpScaledSum : op; }
+  int kernel_op() const { return widened ? hiccl_impl::kOpWidenSum : scaled ? hiccl_impl::kOpScaledSum : op; }
+  // the scale a launch carries: a widened plan's kernels always multiply (by one if unscaled)
+  hiccl_impl::Scale kernel_scale() const { return widened && !scaled ? hiccl_impl::Scale{1.0, 1.0f, 0u} : scale; }
+  bool has_scale() const { return scaled || widened; }
   hiccl_reduce_config_t req;      // hiccl_reduce_plan_set_config / _set_engine / _set_acc (0 = default)
   int engine = HICCL_ENGINE_TILE;  // resolved at upload
   int unroll = hiccl_impl::kDefUnroll;  // TILE packets per lane, resolved at upload
@@ -23,7 +27,8 @@ struct hiccl_reduce_plan {
   int bpc = 1;                     // workgroups per CU, resolved at upload
   int peer = 0;                    // hiccl_reduce_plan_set_peer flags
   int eff_peer = 0;                // peer | the store form plan_store_peer picks, resolved at upload
-  size_t esz = 0;
+  size_t esz = 0;                  // bytes per input element
+  size_t osz = 0;                  // bytes per output element: esz, or 4 on a widened plan
   struct Comp {
     void *out;
     std::vector<const void *> in;

@@ -26,6 +26,15 @@
 // (phase_p: 16 packets native, 8 with the f32 accumulator).  No threshold
 // below has been measured for FP8; DESIGN.md section 5 (M21) records the one
 // FP8 / bf16 comparison.
+//
+// A widened sum (kOpWidenSum, kernels.h: bf16, f16 or FP8 inputs, an f32
+// output) is untuned too.  The dtype it brings is the INPUTS' and every
+// packet and byte count it brings is the OUTPUT's (four elements per packet,
+// 4 * count bytes written), so it takes the rules f64 takes on the same
+// packets -- tuned_type answers false for the operator, phase_p of a native
+// 2-byte or FP8 accumulator is the 16 the widened ops have -- and the store
+// form follows the bytes written.  No threshold below has been measured for
+// it; DESIGN.md section 5 (M22) records the one measurement.
 #include "policy.h"
 
 namespace hiccl_impl {

@@ -38,8 +38,17 @@ int check_op(int dtype, int acc, int op, const std::string &who);
 // and 2-byte types), refused as `who: ...` likewise; *scale (may be NULL): the
 // kernels' argument.
 int check_scale(int dtype, double alpha, const std::string &who, Scale *scale);
+// A widened sum's dtypes (hiccl_reduce_widened: bf16, f16 or FP8 in, f32 out),
+// its accumulation mode (native: the accumulator is f32 as it is) and alpha
+// (NULL: unscaled, the kernels then multiply by 1), refused as `who: ...`
+// likewise; *scale (may be NULL): the kernels' argument.
+bool widen_in_dtype(int dtype);
+int check_widened(int in_dtype, int out_dtype, int acc, const double *alpha, const std::string &who, Scale *scale);
+// Bytes per element a call writes: 4 for a widened sum, else the dtype's.
+inline size_t out_esize(int dtype, int op) { return op == kOpWidenSum ? 4 : esize(dtype); }
 // The one-shot call behind hiccl_reduce_op (scale NULL, `op` checked by the
-// caller) and hiccl_reduce_scaled (op kOpScaledSum): oneshot.cpp.
+// caller), hiccl_reduce_scaled (op kOpScaledSum) and hiccl_reduce_widened (op
+// kOpWidenSum, dtype the inputs', scale never NULL): oneshot.cpp.
 int reduce_call(int dtype, int op, const Scale *scale, void *out, const void *const *in, int n, size_t count,
                 void *stream, const hiccl_reduce_config_t *cfg);
 

@@ -173,6 +173,9 @@ int hiccl_program_add_plan(hiccl_program_t *p, const hiccl_reduce_plan_t *plan) 
     return fail(hipErrorInvalidValue, "program_add_plan: the plan's dtype is neither the program's nor HICCL_BYTES");
   if (plan->req.acc == HICCL_ACC_WIDE)
     return fail(hipErrorInvalidValue, "program_add_plan: programs accumulate natively (HICCL_ACC_NATIVE) only");
+  if (plan->widened)
+    return fail(hipErrorInvalidValue, "program_add_plan: programs take no widened plan (hiccl_reduce_plan_set_out_dtype): "
+                                      "no program kernel changes type");
   if (plan->scaled)
     return fail(hipErrorInvalidValue, "program_add_plan: programs take no scaled plan (hiccl_reduce_plan_set_scale): "
                                       "they have no scale per compute");

@@ -176,8 +176,10 @@ int phase_p(int dtype, int acc) {
 // SUM's kernels are this unit's; MAX and MIN come from reduce_ops.hip, PROD
 // and the bitwise operators from reduce_prod.hip, the scaled sums from
 // reduce_scale.hip; the FP8 types' kernels, whatever the operator, from
-// reduce_f8.hip.
+// reduce_f8.hip; the widened sums (whose dtype is the inputs') from
+// reduce_widen.hip.
 single_fn pick_single(int dtype, int acc, int op, int engine, int block, int unroll, int pol) {
+  if (op == kOpWidenSum) return pick_single_widen(dtype, acc, op, engine, block, unroll, pol);
   if (is_f8(dtype)) return pick_single_f8(dtype, acc, op, engine, block, unroll, pol);
   if (op == kOpScaledSum) return pick_single_scale(dtype, acc, op, engine, block, unroll, pol);
   if (op >= HICCL_OP_PROD) return pick_single_prod(dtype, acc, op, engine, block, unroll, pol);
@@ -186,6 +188,7 @@ single_fn pick_single(int dtype, int acc, int op, int engine, int block, int unr
 }
 
 plan_fn pick_plan(int dtype, int acc, int op, int engine, int unroll, int pol) {
+  if (op == kOpWidenSum) return pick_plan_widen(dtype, acc, op, engine, unroll, pol);
   if (is_f8(dtype)) return pick_plan_f8(dtype, acc, op, engine, unroll, pol);
   if (op == kOpScaledSum) return pick_plan_scale(dtype, acc, op, engine, unroll, pol);
   if (op >= HICCL_OP_PROD) return pick_plan_prod(dtype, acc, op, engine, unroll, pol);
@@ -194,6 +197,7 @@ plan_fn pick_plan(int dtype, int acc, int op, int engine, int unroll, int pol) {
 }
 
 prog_fn pick_prog(int dtype, int op, int unroll) {
+  if (op == kOpWidenSum) return nullptr;  // no program runs a widened plan (hiccl_program_add_plan)
   if (is_f8(dtype)) return pick_prog_f8(dtype, op, unroll);
   if (op >= HICCL_OP_PROD) return pick_prog_prod(dtype, op, unroll);
   if (op != HICCL_OP_SUM) return pick_prog_maxmin(dtype, op, unroll);

@@ -7,7 +7,8 @@
 //
 // The kernels of the two OCP FP8 types (reduce_f8.hip) are compiled into this
 // unit too, behind the scaled sums': the library stays at four code objects
-// with this one last, which the ISA tier of the scaled sums relies on.
+// with this one last, which the ISA tier of the scaled sums relies on.  The
+// widened sums' kernels (reduce_widen.hip) follow them, for the same reason.
 #include "engine.h"
 
 namespace hiccl_impl {
@@ -23,3 +24,4 @@ plan_fn pick_plan_scale(int dtype, int acc, int op, int engine, int unroll, int 
 }  // namespace hiccl_impl
 
 #include "reduce_f8.hip"
+#include "reduce_widen.hip"

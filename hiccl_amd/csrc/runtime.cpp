@@ -150,4 +150,26 @@ int check_buffers(void *out, const void *const *in, int n, size_t count, size_t 
   return 0;
 }
 
+int check_buffers_widened(void *out, const void *const *in, int n, size_t count, size_t esz, size_t osz) {
+  if (!out) return fail(hipErrorInvalidValue, "hiccl_reduce_widened: out is NULL");
+  if ((uintptr_t)out % osz)
+    return fail(hipErrorInvalidValue, "hiccl_reduce_widened: out is not aligned to its element (4 bytes)");
+  if (n < 0) return fail(hipErrorInvalidValue, "hiccl_reduce_widened: n < 0");
+  if (n > 0 && !in) return fail(hipErrorInvalidValue, "hiccl_reduce_widened: in is NULL");
+  if (count > SIZE_MAX / osz)
+    return fail(hipErrorInvalidValue, "hiccl_reduce_widened: count overflows (4 * count does not fit a size_t)");
+  const uintptr_t o0 = (uintptr_t)out, o1 = o0 + count * osz;
+  for (int k = 0; k < n; k++) {
+    const uintptr_t p = (uintptr_t)in[k];
+    if (!p) return fail(hipErrorInvalidValue, "hiccl_reduce_widened: in[" + std::to_string(k) + "] is NULL");
+    if (p % esz)
+      return fail(hipErrorInvalidValue, "hiccl_reduce_widened: in[" + std::to_string(k) + "] is not element-aligned");
+    const uintptr_t p1 = p + count * esz;
+    if (p < o1 && o0 < p1)
+      return fail(hipErrorInvalidValue, "hiccl_reduce_widened: in[" + std::to_string(k) +
+                                            "] overlaps out (a widened sum cannot run in place: the element sizes differ)");
+  }
+  return 0;
+}
+
 }  // namespace hiccl_impl

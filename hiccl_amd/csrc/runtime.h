@@ -50,5 +50,10 @@ inline uint64_t tiles_for(uint64_t npkt, uint64_t unit) {
 }
 // Validate pointers: element alignment, no partial overlap with the output.
 int check_buffers(void *out, const void *const *in, int n, size_t count, size_t esz);
+// A widened sum's pointers (inputs of `esz` bytes per element, an output of
+// `osz`): element alignment on either side, osz * count within a size_t, and
+// NO overlap of the output with any input -- the element sizes differ, so
+// nothing can be summed in place.
+int check_buffers_widened(void *out, const void *const *in, int n, size_t count, size_t esz, size_t osz);
 
 }  // namespace hiccl_impl

@@ -295,6 +295,163 @@ class Compute {
 #endif
 };
 
+// HiCCL::WidenCompute<T>: Compute's object contract for a WIDENED sum -- T
+// inputs (bf16, f16 / _Float16, f8e4m3, f8e5m2), float outputs: every compute
+// writes the in-order f32 sum of its widened inputs, the f32 accumulator as it
+// is (hiccl_reduce_plan_set_out_dtype; low-precision gradient buckets into f32
+// master gradients in one pass).  set_scale multiplies once in f32 at store
+// time.  An output may not overlap an input.  The host port does the same
+// arithmetic in plain C++ (widen_sum, elem_types.h): the same bits.
+// A Comm<T> schedule has no use for it (a schedule moves T between ranks, and
+// a widened sum changes type inside the tree: INTEGRATION.md).
+template <typename T>
+class WidenCompute {
+  static_assert(widenable<T>(), "HiCCL::WidenCompute: bf16, f16 (_Float16), f8e4m3 or f8e5m2 inputs only");
+
+ public:
+  int numcomp = 0;
+  std::vector<std::vector<T *>> inputbuf;
+  std::vector<float *> outputbuf;
+  std::vector<size_t> count;
+
+  WidenCompute() {}
+  ~WidenCompute() {
+#ifndef HICCL_PORT_HOST
+    if (plan) hiccl_reduce_plan_destroy(plan);
+#endif
+  }
+  WidenCompute(const WidenCompute &) = delete;
+  WidenCompute &operator=(const WidenCompute &) = delete;
+
+  // As Compute<T>::add, with a float output.
+  void add(std::vector<T *> &in, float *out, size_t n, int compid, bool peer_inputs = false) {
+    if (CommBench::myid != compid) return;
+    inputbuf.push_back(in);
+    outputbuf.push_back(out);
+    count.push_back(n);
+    numcomp++;
+#ifndef HICCL_PORT_HOST
+    if (!plan) {
+      check(hiccl_reduce_plan_create(&plan, dtype_of<T>(), CommBench::mydevice), "plan_create");
+      if (const char *e = std::getenv("HICCL_ENGINE")) {
+        const std::string v(e);
+        const int eng = v == "tile" ? HICCL_ENGINE_TILE : v == "phase" ? HICCL_ENGINE_PHASE : HICCL_ENGINE_AUTO;
+        check(hiccl_reduce_plan_set_engine(plan, eng), "plan_set_engine");
+      }
+      check(hiccl_reduce_plan_set_out_dtype(plan, HICCL_FLOAT32), "plan_set_out_dtype");  // before the first add
+      if (scaled) check(hiccl_reduce_plan_set_scale(plan, &scale), "plan_set_scale");
+    }
+    if (peer_inputs && !(hiccl_reduce_plan_peer(plan) & HICCL_PEER_LOADS))
+      check(hiccl_reduce_plan_set_peer(plan, hiccl_reduce_plan_peer(plan) | HICCL_PEER_LOADS), "plan_set_peer");
+    check(hiccl_reduce_plan_add(plan, out, (const void *const *)in.data(), (int)in.size(), n), "plan_add");
+#else
+    (void)peer_inputs;
+#endif
+  }
+
+  // out = fl32(sum * (float)alpha) from the next start() on; alpha finite, as a float too.
+  void set_scale(double alpha) {
+    if (!std::isfinite(alpha) || !std::isfinite((float)alpha)) CommBench::die("WidenCompute::set_scale", "alpha must be finite");
+    scaled = true;
+    scale = alpha;
+#ifndef HICCL_PORT_HOST
+    if (plan) check(hiccl_reduce_plan_set_scale(plan, &scale), "plan_set_scale");
+#endif
+  }
+  void clear_scale() {
+    scaled = false;
+#ifndef HICCL_PORT_HOST
+    if (plan) check(hiccl_reduce_plan_set_scale(plan, nullptr), "plan_set_scale");
+#endif
+  }
+
+  void start() {
+    if (!numcomp) return;
+#ifndef HICCL_PORT_HOST
+    check(hiccl_reduce_plan_launch(plan, compute_stream()), "plan_launch");
+#else
+    for (int c = 0; c < numcomp; c++) {
+      float *out = outputbuf[c];
+      T *const *in = inputbuf[c].data();
+      const int k = (int)inputbuf[c].size();
+      const size_t n = count[c];
+#pragma omp parallel for schedule(static)
+      for (size_t i = 0; i < n; i++) out[i] = widen_sum<T>(in, k, i, scaled, scale);
+    }
+#endif
+  }
+
+  void wait() {
+#ifndef HICCL_PORT_HOST
+    if (numcomp) check(hiccl_reduce_plan_sync(plan), "plan_sync");
+#endif
+  }
+
+  // Algorithmic bytes of one start(): sum of count * (n * sizeof(T) + 4).
+  size_t bytes() const {
+    size_t b = 0;
+    for (int c = 0; c < numcomp; c++) b += count[c] * (inputbuf[c].size() * sizeof(T) + sizeof(float));
+    return b;
+  }
+
+  // Compute<T>::report's table.
+  void report() {
+    std::vector<int> nc(CommBench::numproc), ni(CommBench::numproc);
+    int numinput = 0;
+    for (auto &v : inputbuf) numinput += (int)v.size();
+    MPI_Allgather(&numcomp, 1, MPI_INT, nc.data(), 1, MPI_INT, CommBench::comm_mpi);
+    MPI_Allgather(&numinput, 1, MPI_INT, ni.data(), 1, MPI_INT, CommBench::comm_mpi);
+    if (CommBench::myid == CommBench::printid) {
+      std::printf("numcomp: ");
+      for (int p = 0; p < CommBench::numproc; p++) std::printf("%d(%d) ", nc[p], ni[p]);
+      std::printf("\n\n");
+    }
+  }
+
+  // Compute<T>::measure(warmup, numiter), pricing n * sizeof(T) + 4 bytes per
+  // element, summed over ranks; the roofline line prices the busiest rank.
+  void measure(int warmup, int numiter) {
+    report();
+    unsigned long busiest = (unsigned long)bytes(), tot = (unsigned long)bytes();
+    MPI_Allreduce(MPI_IN_PLACE, &busiest, 1, MPI_UNSIGNED_LONG, MPI_MAX, CommBench::comm_mpi);
+    MPI_Allreduce(MPI_IN_PLACE, &tot, 1, MPI_UNSIGNED_LONG, MPI_SUM, CommBench::comm_mpi);
+    std::vector<double> times;
+    if (CommBench::myid == CommBench::printid)
+      std::printf("Measure Widened Reduction Kernel\n%d warmup iterations (in order)\n", warmup);
+    for (int it = -warmup; it < numiter; it++) {
+#ifndef HICCL_PORT_HOST
+      CommBench::hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+#endif
+      MPI_Barrier(CommBench::comm_mpi);
+      double t0 = MPI_Wtime();
+      start();
+      double st = MPI_Wtime() - t0;
+      wait();
+      double t = MPI_Wtime() - t0;
+      MPI_Allreduce(MPI_IN_PLACE, &st, 1, MPI_DOUBLE, MPI_MAX, CommBench::comm_mpi);
+      MPI_Allreduce(MPI_IN_PLACE, &t, 1, MPI_DOUBLE, MPI_MAX, CommBench::comm_mpi);
+      if (it < 0) {
+        if (CommBench::myid == CommBench::printid) std::printf("startup %.2e warmup: %e\n", st, t);
+      } else {
+        times.push_back(t);
+      }
+    }
+    Compute<float>::roofline_bytes = (double)busiest;
+    Compute<float>::print_times(times, (double)tot);
+    Compute<float>::roofline_bytes = 0;
+  }
+
+ private:
+  bool scaled = false;
+  double scale = 1.0;
+#ifndef HICCL_PORT_HOST
+  hiccl_reduce_plan_t *plan = nullptr;
+  static void check(int e, const char *what) {
+    if (e) CommBench::die(what, hiccl_last_error());
+  }
+#endif
+};
+
 }  // namespace HiCCL
 
 #endif  // HICCL_COMPUTE_H

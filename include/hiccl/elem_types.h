@@ -7,6 +7,7 @@
 #ifndef HICCL_ELEM_TYPES_H
 #define HICCL_ELEM_TYPES_H
 
+#include <cstddef>
 #include <cstdint>
 #include <cstring>
 #include <type_traits>
@@ -195,6 +196,31 @@ inline T scale_finish(T s, double alpha) {
     volatile float p = (float)s * (float)alpha;
     return (T)p;
   }
+}
+
+// The element types a widened sum reads (WidenCompute<T>, compute.h; the C
+// ABI's hiccl_reduce_widened): the 2-byte and 1-byte floating types.
+template <typename T>
+constexpr bool widenable() {
+  return std::is_same<T, bf16>::value || std::is_same<T, f16>::value || std::is_same<T, f8e4m3>::value ||
+         std::is_same<T, f8e5m2>::value
+#ifdef __FLT16_MANT_DIG__
+         || std::is_same<T, _Float16>::value
+#endif
+      ;
+}
+
+// One element of a widened sum, the host port's arithmetic: widen every input
+// through its `operator float` (exact), add in f32 in list order from +0, and
+// for a scaled sum multiply once by (float)alpha (scale_finish<float>).
+// `volatile` keeps every partial sum a rounded float on hosts that evaluate in
+// a wider format.
+template <typename T>
+inline float widen_sum(T *const *in, int k, size_t i, bool scaled, double alpha) {
+  static_assert(widenable<T>(), "HiCCL::widen_sum: bf16, f16 (_Float16), f8e4m3 or f8e5m2 inputs only");
+  volatile float acc = 0.0f;
+  for (int j = 0; j < k; j++) acc = acc + (float)in[j][i];
+  return scaled ? scale_finish<float>(acc, alpha) : (float)acc;
 }
 
 }  // namespace HiCCL

@@ -311,6 +311,49 @@ int hiccl_reduce_auto_choice_scaled(int dtype, const hiccl_reduce_config_t *cfg,
                                     int *store_policy);
 
 /* ----------------------------------------------------------------------
+ * Widened sums: low-precision inputs summed into an f32 OUTPUT -- bf16, fp16
+ * or FP8 gradient buckets reduced into f32 master gradients ("reduce dtype =
+ * fp32") in one pass, with no converted copy of the inputs.
+ *
+ *   in_dtype   HICCL_BFLOAT16, HICCL_FLOAT16, HICCL_FLOAT8_E4M3 or
+ *              HICCL_FLOAT8_E5M2;  out_dtype  HICCL_FLOAT32;  SUM only.
+ *   s32[i]     (((+0.0f + widen(in[0][i])) + widen(in[1][i])) + ...): widen is
+ *              the exact f32 value of the element, every add one IEEE f32 add
+ *              (nearest even) in list order from +0 -- the accumulator of the
+ *              HICCL_ACC_WIDE sum of the same inputs before its final rounding,
+ *              and the f32 SUM of the widened inputs, bit for bit.
+ *   out[i]     s32[i] (alpha == NULL), or fl32(s32[i] * a32), a32 =
+ *              (float)*alpha, as hiccl_reduce_scaled.
+ * Subnormal inputs and results are kept, all -0 inputs give +0, Inf + -Inf is
+ * NaN, an e4m3 NaN code widens to a NaN, nothing is clamped (an f32 sum of FP8
+ * values cannot overflow for any n); NaN outputs compare by NaN-ness.  n == 0
+ * writes +0.0f, scaled a zero with alpha's sign.  The unscaled form runs the
+ * scaled kernels with a32 = 1.0f: the same words, NaN payloads aside.
+ *
+ * Refused with hipErrorInvalidValue and a message, before any device work: an
+ * out_dtype other than HICCL_FLOAT32, an in_dtype outside the four, cfg->acc
+ * other than HICCL_ACC_NATIVE (a widened sum always accumulates in f32), a
+ * non-finite alpha (hiccl_reduce_scaled's rules) and a config whose shape the
+ * kernels lack (they are untuned: TILE 256 x 4, PHASE's default chunk of 16
+ * packets per lane, nt or system-scope write-through stores) -- refused, never
+ * replaced.  `out` must be 4-byte aligned, every input aligned to its element.
+ * NO ALIASING: the element sizes differ, so no input can be summed in place --
+ * any overlap of [out, out + 4 * count) with an input's [in, in + esz * count)
+ * is refused, as is a count whose 4 * count does not fit a size_t.
+ * The layout is the other kernels' with the packets 16-B aligned on the output:
+ * a packet is FOUR elements (head <= 3 scalars, a TILE tile 4,096 elements, a
+ * PHASE chunk 32,768).  The store-form size rule counts the bytes WRITTEN
+ * (4 * count).  n > 64 runs on the plan kernel; n <= 64 can be captured into a
+ * graph.  hiccl_reduce_auto_choice_widened answers on the host what the call
+ * resolves to: units counted in output packets, the untuned rules HICCL_FLOAT64
+ * takes; no AUTO threshold has been measured for these kernels. */
+int hiccl_reduce_widened(int in_dtype, int out_dtype, const double *alpha, void *out, const void *const *in,
+                         int n, size_t count, void *stream, const hiccl_reduce_config_t *cfg);
+int hiccl_reduce_auto_choice_widened(int in_dtype, const hiccl_reduce_config_t *cfg, size_t count, double n,
+                                     int cus, int *engine, int *unroll, int *blocks_per_cu, int *dynamic,
+                                     int *store_policy);
+
+/* ----------------------------------------------------------------------
  * Persistent plan: the C-ABI counterpart of the reference's Compute<T>
  * (compute.h:26-204).  A plan holds any number of registered computes and
  * launches ALL of them in ONE kernel (one launch per pipeline step instead
@@ -371,6 +414,23 @@ int hiccl_reduce_plan_op(const hiccl_reduce_plan_t *plan);
  * an unscaled one, -1 for NULL. */
 int hiccl_reduce_plan_set_scale(hiccl_reduce_plan_t *plan, const double *alpha);
 int hiccl_reduce_plan_scale(const hiccl_reduce_plan_t *plan, double *alpha);
+/* The plan's output dtype (hiccl_reduce_widened): HICCL_FLOAT32 on a plan of
+ * HICCL_BFLOAT16, HICCL_FLOAT16, HICCL_FLOAT8_E4M3 or HICCL_FLOAT8_E5M2 makes
+ * it a WIDENED plan -- every compute reads the plan's dtype and writes f32.
+ * Before the first add only: an output's alignment and overlap rules depend on
+ * it, so it is refused on a plan that holds a compute.  Refused too: any other
+ * out_dtype, a plan of another dtype, a plan whose op is not SUM or whose acc is HICCL_ACC_WIDE, and
+ * a plan whose config names a shape the widened kernels lack.  A widened plan
+ * takes set_scale and set_peer; set_op refuses anything but SUM, set_acc and
+ * set_config refuse HICCL_ACC_WIDE and TILE shapes other than 256 x 4; add
+ * applies hiccl_reduce_widened's buffer rules (out 4-byte aligned, no overlap
+ * at all); launch, enqueue, launch_each and sync work as on any plan;
+ * hiccl_reduce_plan_bytes prices count * (n * esz + 4) per compute;
+ * hiccl_program_add_plan refuses it (no program kernel changes type).
+ * hiccl_reduce_plan_out_dtype: the output dtype (the plan's own unless
+ * widened), -1 for NULL. */
+int hiccl_reduce_plan_set_out_dtype(hiccl_reduce_plan_t *plan, int out_dtype);
+int hiccl_reduce_plan_out_dtype(const hiccl_reduce_plan_t *plan);
 /* Engine for the plan's launches (hiccl_engine_t; default AUTO, decided from
  * the total packets of all computes at the first launch after an add). */
 int hiccl_reduce_plan_set_engine(hiccl_reduce_plan_t *plan, int engine);
@@ -444,7 +504,8 @@ int hiccl_reduce_plan_sync(hiccl_reduce_plan_t *plan);
 void *hiccl_reduce_plan_stream(hiccl_reduce_plan_t *plan);
 int hiccl_reduce_plan_numcomp(const hiccl_reduce_plan_t *plan);
 /* Sum over computes of count * (n + 1) * sizeof(T): the bytes the reference's
- * measure(warmup, numiter) overload (compute.h:197-203) prices. */
+ * measure(warmup, numiter) overload (compute.h:197-203) prices.  A widened
+ * plan: count * (n * sizeof(T) + 4). */
 size_t hiccl_reduce_plan_bytes(const hiccl_reduce_plan_t *plan);
 void hiccl_reduce_plan_destroy(hiccl_reduce_plan_t *plan);
 

@@ -4,17 +4,24 @@ the C5 pipeline step, config 3 against config 2 on one box), dispatched from
 bench.py (`--nway`, `--chunks`, `--roundtrip`, `--c3vsc2`, `--progstep`).
 They share bench.py's buckets, timers and ceilings (imported as `B`) and
 print one JSON line per case; the driver's line is bench.py's default run.
+
+`widen` (the widened sums against the convert-then-reduce path) is not one of
+bench.py's flags; it runs from here:
+
+    python tools/bench_modes.py widen [--steps K] [--warmup W] [--rounds R] [--log2count L]
 """
 import ctypes
 import json
 import os
+import sys
 
 import numpy as np
 import torch
 
-import bench as B
-import hiccl_amd
-from hiccl_amd import _lib as L
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))  # bench.py, when run from here
+import bench as B  # noqa: E402
+import hiccl_amd  # noqa: E402
+from hiccl_amd import _lib as L  # noqa: E402
 
 def nway(args):
     """Config 3: N in 2..64 inputs x 2^26 fp32 (256 MiB each)."""
@@ -389,3 +396,77 @@ def progstep(args):
     for pr in (p_copy, p_comp, p_tail, q_copy, q_comp):
         pr.close()
     return 0
+
+
+def widen(args):
+    """Widened sums on config 2's element count: 8 x 2^28 bf16 -> f32 (5 GiB of
+    algorithmic traffic) and 8 x 2^28 e4m3 -> f32 (3 GiB), under AUTO.  Three
+    legs per type, alternating within this process for `--rounds` rounds of
+    `--steps` launches timed by device events:
+      widened       hiccl_amd.reduce_widened, one kernel;
+      convert_f32   what a caller has without it: x.float() per input into
+                    preallocated f32 buffers, then hiccl_amd.reduce in f32 (the
+                    events enclose the eight conversions and the kernel);
+      f32_kernel    that f32 reduction alone: config 2's kernel at the same
+                    element count, 9 GiB -- the yardstick for bytes per second.
+    One JSON line per type; the widened output is compared with the f32 path's
+    bit for bit (both are in-order f32 sums) before anything is timed."""
+    n, count = 8, 1 << getattr(args, "log2count", 28)
+    rounds = getattr(args, "rounds", 5)
+    for name, dtype in (("bf16", torch.bfloat16), ("e4m3", torch.float8_e4m3fn)):
+        esz = torch.empty((), dtype=dtype).element_size()
+        ins, _ = B.make_bucket(n, count, dtype)
+        f_ins, f_out = hiccl_amd.bucket(n, count, torch.float32)
+        out = torch.empty(count, dtype=torch.float32, device="cuda")
+
+        def convert():
+            for a, b in zip(f_ins, ins):
+                a.copy_(b)  # the dtype conversion kernel: esz bytes read, 4 written per element
+
+        legs = {
+            "widened": lambda: hiccl_amd.reduce_widened(out, ins),
+            "convert_f32": lambda: (convert(), hiccl_amd.reduce(f_out, f_ins)),
+            "f32_kernel": lambda: hiccl_amd.reduce(f_out, f_ins),
+        }
+        legs["convert_f32"]()
+        legs["widened"]()
+        torch.cuda.synchronize()
+        exact = bool(torch.equal(out.view(torch.int32), f_out.view(torch.int32)))
+        ms = {k: [] for k in legs}
+        for _ in range(rounds):
+            for k, fn in legs.items():
+                _, t = B.time_launches(fn, args.steps, args.warmup)
+                ms[k].append(float(np.median(t)))
+        med = {k: float(np.median(v)) for k, v in ms.items()}
+        alg = count * (n * esz + 4)
+        f32_alg = count * (n + 1) * 4
+        rate = alg / (med["widened"] * 1e-3) / 1e9
+        f32_rate = f32_alg / (med["f32_kernel"] * 1e-3) / 1e9
+        print(json.dumps({
+            "mode": "widen", "in_dtype": name, "n": n, "count": count, "rounds": rounds, "steps": args.steps,
+            "auto_choice": hiccl_amd.auto_choice(dtype, count, n, out_dtype=torch.float32),
+            "bit_exact_vs_f32_path": exact,
+            "widened_ms": round(med["widened"], 4), "widened_ms_per_round": [round(v, 4) for v in ms["widened"]],
+            "convert_f32_ms": round(med["convert_f32"], 4),
+            "convert_f32_ms_per_round": [round(v, 4) for v in ms["convert_f32"]],
+            "f32_kernel_ms": round(med["f32_kernel"], 4), "f32_kernel_ms_per_round": [round(v, 4) for v in ms["f32_kernel"]],
+            "widened_over_convert": round(med["widened"] / med["convert_f32"], 4),
+            "widened_over_f32_kernel": round(med["widened"] / med["f32_kernel"], 4),
+            "algorithmic_bytes": alg, "widened_GBps": round(rate, 1), "f32_kernel_GBps": round(f32_rate, 1),
+            "rate_over_f32_kernel": round(rate / f32_rate, 4),
+            "device": torch.cuda.get_device_properties(0).name}), flush=True)
+        del ins, f_ins, f_out, out
+        torch.cuda.empty_cache()
+    return 0
+
+
+if __name__ == "__main__":
+    import argparse
+    ap = argparse.ArgumentParser(description="modes that bench.py has no flag for")
+    ap.add_argument("mode", choices=["widen"])
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--log2count", type=int, default=28)
+    a = ap.parse_args()
+    raise SystemExit(widen(a))
