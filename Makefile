@@ -18,7 +18,8 @@ $(PROBE): tools/hbm_probe.hip
 # (engine.h) -- reduce.hip, the SUM kernels, reduce_ops.hip, the MAX / MIN
 # kernels, reduce_prod.hip, the PROD and bitwise kernels, and reduce_scale.hip,
 # the scaled sums, which also takes in reduce_f8.hip, the OCP FP8 types, and
-# reduce_widen.hip, the widened sums (the library keeps four code objects, the
+# reduce_widen.hip, the widened sums, and reduce_accum.hip, the accumulating
+# ones (the library keeps four code objects, the
 # scaled sums' last), compiled side by
 # side (reduce.hip the longest) -- and the host files (seconds each), as
 # objects under build/obj, linked once.  The link order is the order of the
@@ -81,7 +82,8 @@ CPP_BINS = build/plan_dump build/collectives_host build/collectives_host_f32 bui
            build/scale_finish build/scale_compute_host build/scale_compute_hip \
            build/f8_add build/f8_compute_host build/f8_compute_hip \
            build/types_comm_host build/types_comm_hip \
-           build/widen_sum build/widen_sum_hip
+           build/widen_sum build/widen_sum_hip \
+           build/accum_sum build/accum_sum_hip
 
 cpp: $(CPP_BINS)
 
@@ -237,6 +239,17 @@ build/widen_sum: tests/cpp/widen_sum.cpp $(HDRS)
 	$(CXX) $(CXXFLAGS) -fopenmp -DHICCL_PORT_HOST -o $@ $< $(MPI_LINK)
 
 build/widen_sum_hip: tests/cpp/widen_sum.cpp $(HDRS) $(LIB)
+	@mkdir -p build
+	$(CXX) $(CXXFLAGS) $(HIP_HOST) -o $@ $< $(HIP_LINK) $(MPI_LINK)
+
+# Accumulating widened sums: WidenCompute<T>::set_accumulate (out += alpha *
+# sum) on the host port -- a stand-alone program that tests/test_accum_cpu.py
+# also builds with sanitizers -- and on the GPU (tests/test_accum_gpu.py)
+build/accum_sum: tests/cpp/accum_sum.cpp $(HDRS)
+	@mkdir -p build
+	$(CXX) $(CXXFLAGS) -fopenmp -DHICCL_PORT_HOST -o $@ $< $(MPI_LINK)
+
+build/accum_sum_hip: tests/cpp/accum_sum.cpp $(HDRS) $(LIB)
 	@mkdir -p build
 	$(CXX) $(CXXFLAGS) $(HIP_HOST) -o $@ $< $(HIP_LINK) $(MPI_LINK)
 

@@ -188,7 +188,16 @@ def _check_widened_config(config):
         raise ValueError("hiccl: a widened sum always accumulates in f32: leave acc at HICCL_ACC_NATIVE")
 
 
-def reduce_widened(out, inputs, count=None, stream=None, config=None, scale=None):
+def _check_accumulate(accumulate, widened=True):
+    """``accumulate=`` is a bool, and goes with a widened sum only."""
+    if not isinstance(accumulate, bool):
+        raise TypeError(f"hiccl: accumulate must be a bool, not {type(accumulate).__name__}")
+    if accumulate and not widened:
+        raise ValueError("hiccl: only a widened sum accumulates: accumulate=True goes with out_dtype=torch.float32 "
+                         "(a same-type sum accumulates by passing out as input 0)")
+
+
+def reduce_widened(out, inputs, count=None, stream=None, config=None, scale=None, accumulate=False):
     """out[:count] = ((0.0f + float(inputs[0])) + float(inputs[1])) + ... in the
     list order, every add an f32 add: bf16, f16 or FP8 ``inputs`` (one dtype)
     summed into a ``torch.float32`` ``out`` in one pass (hiccl_reduce_widened)
@@ -201,6 +210,10 @@ def reduce_widened(out, inputs, count=None, stream=None, config=None, scale=None
     nothing runs in place).  Asynchronous on ``stream``; ``config`` as
     :func:`reduce`'s, ``acc`` left native.  The kernels are untuned: a config
     that names a shape they lack raises HicclError.
+
+    ``accumulate=True``: ``out += scale * sum`` (hiccl_reduce_accumulate) --
+    the sum is finished first, scaled, then added to ``out`` as it was: three
+    separately rounded f32 operations.  Every call adds once more.
     """
     _check_tensor(out, "out")
     if count is None:
@@ -229,13 +242,15 @@ def reduce_widened(out, inputs, count=None, stream=None, config=None, scale=None
         raise ValueError(f"hiccl: out has {out.numel()} < count={count} elements")
     with torch.cuda.device(out.device):  # the library launches on the current device
         reduce_widened_ptrs(L.DTYPE_OF_TORCH[in_dtype], out.data_ptr(), ptrs, count,
-                            stream=_stream_handle(stream, out.device).value or 0, config=config, scale=scale)
+                            stream=_stream_handle(stream, out.device).value or 0, config=config, scale=scale,
+                            accumulate=accumulate)
     return out
 
 
 def reduce_widened_ptrs(in_dtype_code, out_ptr, in_ptrs, count, stream=None, config=None, scale=None,
-                        out_dtype_code=L.HICCL_FLOAT32):
+                        out_dtype_code=L.HICCL_FLOAT32, accumulate=False):
     """Raw-pointer form of :func:`reduce_widened` (pointers already offset)."""
+    _check_accumulate(accumulate)
     _check_widened(in_dtype_code, out_dtype_code)
     _check_widened_config(config)
     alpha = None
@@ -243,9 +258,10 @@ def reduce_widened_ptrs(in_dtype_code, out_ptr, in_ptrs, count, stream=None, con
         alpha = ctypes.byref(ctypes.c_double(_check_scale(scale, in_dtype_code)))
     tab = _ptr_table(list(in_ptrs))
     cfg = ctypes.byref(L.ReduceConfig(**config)) if config is not None else None
-    rc = L.lib().hiccl_reduce_widened(int(in_dtype_code), int(out_dtype_code), alpha, ctypes.c_void_p(out_ptr), tab,
-                                      len(in_ptrs), count, _stream_handle(stream), cfg)
-    L.check(rc, "hiccl_reduce_widened")
+    fn = L.lib().hiccl_reduce_accumulate if accumulate else L.lib().hiccl_reduce_widened
+    rc = fn(int(in_dtype_code), int(out_dtype_code), alpha, ctypes.c_void_p(out_ptr), tab, len(in_ptrs), count,
+            _stream_handle(stream), cfg)
+    L.check(rc, "hiccl_reduce_accumulate" if accumulate else "hiccl_reduce_widened")
 
 
 def bucket(n, count, dtype=torch.float32, device=None):
@@ -267,7 +283,8 @@ def bucket(n, count, dtype=torch.float32, device=None):
     return views[:n], views[n]
 
 
-def auto_choice(dtype, count, n, config=None, cus=256, op=L.HICCL_OP_SUM, scale=False, out_dtype=None):
+def auto_choice(dtype, count, n, config=None, cus=256, op=L.HICCL_OP_SUM, scale=False, out_dtype=None,
+                accumulate=False):
     """What a one-shot call (and a one-compute plan at TILE unroll 2 / 4 or
     AUTO) resolves to on a GPU of ``cus`` CUs, without a device:
     ``hiccl_reduce_auto_choice_ex`` (``op`` other than SUM:
@@ -277,7 +294,10 @@ def auto_choice(dtype, count, n, config=None, cus=256, op=L.HICCL_OP_SUM, scale=
     with engine, unroll, blocks_per_cu, dynamic and store_policy (2 nt, 4
     write-through); raises HicclError for a config no kernel has.
     ``out_dtype`` (torch.float32 with a bf16, f16 or FP8 ``dtype``): a widened
-    sum, ``hiccl_reduce_auto_choice_widened`` -- the same answer scaled or not."""
+    sum, ``hiccl_reduce_auto_choice_widened`` -- the same answer scaled or not;
+    with ``accumulate=True`` ``hiccl_reduce_auto_choice_accumulate``, the same
+    answer again."""
+    _check_accumulate(accumulate, out_dtype is not None)
     dt = L.DTYPE_OF_TORCH[dtype] if isinstance(dtype, torch.dtype) else int(dtype)
     cfg = ctypes.byref(L.ReduceConfig(**config)) if config else None
     out = [ctypes.c_int() for _ in range(5)]
@@ -286,7 +306,8 @@ def auto_choice(dtype, count, n, config=None, cus=256, op=L.HICCL_OP_SUM, scale=
         if op != L.HICCL_OP_SUM:
             raise ValueError("hiccl: only sums are widened: out_dtype= goes with HICCL_OP_SUM")
         _check_widened_config(config)
-        rc = L.lib().hiccl_reduce_auto_choice_widened(dt, cfg, count, float(n), cus, *[ctypes.byref(v) for v in out])
+        fn = L.lib().hiccl_reduce_auto_choice_accumulate if accumulate else L.lib().hiccl_reduce_auto_choice_widened
+        rc = fn(dt, cfg, count, float(n), cus, *[ctypes.byref(v) for v in out])
     elif scale:
         _check_scale(1.0, dtype if isinstance(dtype, torch.dtype) else dt, op)
         rc = L.lib().hiccl_reduce_auto_choice_scaled(dt, cfg, count, float(n), cus, *[ctypes.byref(v) for v in out])
@@ -314,7 +335,9 @@ class Compute:
     """
 
     def __init__(self, dtype=torch.float32, device=None, myid=0, acc=L.HICCL_ACC_NATIVE,
-                 engine=L.HICCL_ENGINE_AUTO, config=None, op=L.HICCL_OP_SUM, scale=None, out_dtype=None):
+                 engine=L.HICCL_ENGINE_AUTO, config=None, op=L.HICCL_OP_SUM, scale=None, out_dtype=None,
+                 accumulate=False):
+        _check_accumulate(accumulate, out_dtype is not None)
         self.dtype = dtype
         self.code = L.DTYPE_OF_TORCH[dtype]
         if scale is not None:
@@ -353,6 +376,24 @@ class Compute:
                     "plan_set_out_dtype")
         if scale is not None:
             self.set_scale(scale)
+        if accumulate:
+            self.set_accumulate(True)
+
+    def set_accumulate(self, on):
+        """Accumulation of a widened plan (hiccl_reduce_plan_set_accumulate):
+        every compute writes ``out + scale * sum`` from the next launch on
+        (``start(each=True)`` too), and every launch adds once more; ``False``
+        goes back to overwriting.  At any time, like :meth:`set_scale`.  A
+        widened plan only, and never with HICCL_PEER_STORES."""
+        _check_accumulate(on, self.out_dtype != self.dtype)
+        if on and self.peer() & L.HICCL_PEER_STORES:
+            raise ValueError("hiccl: an accumulating plan takes no HICCL_PEER_STORES (the old output is read where it "
+                             "is written: keep it in local memory)")
+        L.check(L.lib().hiccl_reduce_plan_set_accumulate(self._plan, 1 if on else 0), "plan_set_accumulate")
+
+    def accumulate(self):
+        """Does the plan accumulate (hiccl_reduce_plan_accumulate)?"""
+        return L.lib().hiccl_reduce_plan_accumulate(self._plan) == 1
 
     def set_scale(self, scale):
         """Scale of the plan's sums (hiccl_reduce_plan_set_scale): every
@@ -402,7 +443,10 @@ class Compute:
         """Peer-memory policy of the plan's launches (hiccl_reduce_plan_set_peer):
         HICCL_PEER_STORES (outputs in another GPU's memory: system-scope
         write-through stores) | HICCL_PEER_LOADS (inputs there: system-scope
-        loads).  Same results."""
+        loads).  Same results.  An accumulating plan takes HICCL_PEER_LOADS only."""
+        if flags & L.HICCL_PEER_STORES and self.accumulate():
+            raise ValueError("hiccl: an accumulating plan takes no HICCL_PEER_STORES (the old output is read where it "
+                             "is written: keep it in local memory)")
         L.check(L.lib().hiccl_reduce_plan_set_peer(self._plan, flags), "plan_set_peer")
 
     def peer(self):
@@ -471,7 +515,7 @@ class Compute:
 
     def bytes(self):
         """Sum of count * (n + 1) * sizeof(T) (compute.h:197-203); a widened
-        plan: count * (n * sizeof(T) + 4)."""
+        plan: count * (n * sizeof(T) + 4), an accumulating one + 8."""
         return L.lib().hiccl_reduce_plan_bytes(self._plan)
 
     def report(self):

@@ -7,8 +7,9 @@
 // (kPartSum), reduce_ops.hip for the MAX / MIN ops (kPartMaxMin),
 // reduce_prod.hip for PROD and the bitwise ops (kPartProd),
 // reduce_scale.hip for the post-scaled sums (kPartScale), reduce_f8.hip
-// for every op of the two OCP FP8 types (kPartF8) and reduce_widen.hip for the
-// widened sums (kPartWiden; the last two are included from reduce_scale.hip).  All
+// for every op of the two OCP FP8 types (kPartF8), reduce_widen.hip for the
+// widened sums (kPartWiden) and reduce_accum.hip for the accumulating widened
+// sums (kPartAccum; the last three are included from reduce_scale.hip).  All
 // take their ops from the one list below (with_elem<PART>), so a type or an
 // operator is still added in one place.  Everything here is in an anonymous
 // namespace: a kernel belongs to the unit that instantiates it.
@@ -943,6 +944,55 @@ typedef OpWiden<WidenBF16> OpBF16ToF32;
 typedef OpWiden<WidenF16> OpF16ToF32;
 template <int FMT> using OpF8ToF32 = OpWiden<WidenF8<FMT>>;
 
+// ------------------------------------------------ accumulating widened sums --
+// out = fl32(p + fl32(s32 * a32)), p the OUTPUT as it was before the launch
+// (hiccl_reduce_accumulate, hiccl_reduce_plan_set_accumulate): OpWiden's sum,
+// bit for bit, finished first; then the scale, on the new contribution alone;
+// then ONE add of the old output -- three separately rounded f32 operations.
+// The product passes through opaque_f32 as the scaled sums' does, so the
+// multiply and the add that follows it cannot contract into v_fma_f32 /
+// v_pk_fma_f32 (a different word: one rounding less).  p is not addend 0 of
+// the fold (fl32(fl32(p + x0) + x1) differs from fl32(p + fl32(x0 + x1))).
+// An op of this family sets kAccum: the engines then read the old packet
+// through the OUTPUT's own descriptor (the range check of the store, one
+// buffer_load_dwordx4 per packet) and hand it to pack(); sstore() reads the
+// scalar head / tail element it is about to overwrite.  A unit is read,
+// modified and written once per launch: head, body units and tail are
+// disjoint, and both schedules hand every unit out once.
+// A family of its own, not a flag of OpWiden: the widened kernels stay
+// instruction for instruction what they are, and the kernels' names differ.
+template <class Op, class = void>
+struct accumulates : std::false_type {};
+template <class Op>
+struct accumulates<Op, std::enable_if_t<Op::kAccum>> : std::true_type {};
+
+template <class W>
+struct OpWidenAccum : OpWiden<W> {
+  static constexpr bool kAccum = true;
+  static constexpr bool kHalfChunk = true;  // phase_p_of: the old packets are held over the sweep (chunk_body)
+  __device__ static u32x4 pack(f32x4 a, float a32, u32x4 old) {
+    f32x4 r;
+#pragma unroll
+    for (int i = 0; i < 4; i++) r[i] = opaque_f32(a[i] * a32);
+    return __builtin_bit_cast(u32x4, __builtin_bit_cast(f32x4, old) + r);
+  }
+  __device__ static void sstore(char *p, float a, float a32) {
+    const float r = opaque_f32(a * a32);
+    gst<float>(p, gld<float>(p) + r);
+  }
+};
+
+typedef OpWidenAccum<WidenBF16> OpBF16AccF32;
+typedef OpWidenAccum<WidenF16> OpF16AccF32;
+template <int FMT> using OpF8AccF32 = OpWidenAccum<WidenF8<FMT>>;
+
+// The old output packets of a unit, one buffer_load_dwordx4 each (kAccum ops).
+template <class Op, int U, int POL>
+__device__ __forceinline__ void load_old(u32x4 (&old)[U], rsrc_t w, const uint32_t (&voff)[U]) {
+#pragma unroll
+  for (int u = 0; u < U; u++) old[u] = load_pkt<POL>(w, voff[u]);
+}
+
 // ----------------------------------------------------------- tile engine --
 //
 // A compute is split as [head scalars | npkt 16-B packets | tail scalars],
@@ -1066,6 +1116,15 @@ __device__ __forceinline__ void tile_body(char *outb, Inputs in, uint32_t n, uin
   // as a VGPR copy joined over the switch's cases, and with it a waterfall
   // loop around each of their stores (4 SGPRs held over the tile instead).
   const rsrc_t w = make_rsrc(outb + tile_off, tile_bytes);
+  // An accumulating op's old output packets are asked for here, ahead of the
+  // first group's loads, so they come back under the inputs' latency: with up
+  // to 8 inputs that group is the tile's last, with more the 4 * U VGPRs are
+  // held over the earlier groups (no spill at 256 x 4).
+  [[maybe_unused]] u32x4 old[accumulates<Op>::value ? U : 1];
+  if constexpr (accumulates<Op>::value) {
+    load_old<Op, U, POL>(old, w, voff);
+    __builtin_amdgcn_sched_barrier(0);
+  }
   // groups of GM inputs: at most 32 packets per lane in flight (U = 8: 4
   // inputs, U = 16: 2), so wide tiles stay within the register file
   constexpr uint32_t GM = U >= 8 ? 32 / U : 8;
@@ -1083,7 +1142,10 @@ __device__ __forceinline__ void tile_body(char *outb, Inputs in, uint32_t n, uin
   }
   before_store();
 #pragma unroll
-  for (int u = 0; u < U; u++) store_pkt<POL>(w, voff[u], pack_fin<Op>(acc[u], fin));
+  for (int u = 0; u < U; u++) {
+    if constexpr (accumulates<Op>::value) store_pkt<POL>(w, voff[u], Op::pack(acc[u], fin, old[u]));
+    else store_pkt<POL>(w, voff[u], pack_fin<Op>(acc[u], fin));
+  }
 }
 
 // Input-phased chunk (the default engine for large buckets).  A chunk =
@@ -1122,6 +1184,17 @@ __device__ __forceinline__ void chunk_body(char *outb, Inputs in, uint32_t n, ui
   typename Op::acc_t acc[P];
 #pragma unroll
   for (int p = 0; p < P; p++) acc[p] = Op::zero();
+  // An accumulating op reads the old output through the store's descriptor,
+  // which it therefore builds here.  The loads go out in the sweep's LAST pass,
+  // behind the x loads -- the slot that holds the zero-range load when n is
+  // even -- so the old packets are one more stream of the ping-pong: in flight
+  // while the last one or two inputs are added.  They are a loop-carried value
+  // (4 VGPRs per packet over every pass), which is why these ops take the half
+  // chunk (kHalfChunk): at P = 16 the bf16 kernel came out at 256 VGPRs with 24
+  // B of scratch, and a peeled last pass did worse (184 B).
+  [[maybe_unused]] u32x4 old[accumulates<Op>::value ? P : 1];
+  [[maybe_unused]] rsrc_t wo;
+  if constexpr (accumulates<Op>::value) wo = make_rsrc(outb + off, nbytes);
   if (n > 0) {
     in_pkt_t<Op> x[P], y[P];
     const uint64_t ioff = in_bytes<Op>(off);
@@ -1130,6 +1203,9 @@ __device__ __forceinline__ void chunk_body(char *outb, Inputs in, uint32_t n, ui
       rsrc_t r = make_rsrc(in(0) + ioff, ibytes);
 #pragma unroll
       for (int p = 0; p < P; p++) x[p] = load_in<Op, POL>(r, voff[p]);
+    }
+    if constexpr (accumulates<Op>::value) {
+      if (n == 1) load_old<Op, P, POL>(old, wo, voff);
     }
     uint32_t j = 0;
     for (; j + 2 <= n; j += 2) {  // x: input j in flight
@@ -1148,6 +1224,9 @@ __device__ __forceinline__ void chunk_body(char *outb, Inputs in, uint32_t n, ui
       rsrc_t rx = make_rsrc(in(more ? j + 2 : j + 1) + ioff, more ? ibytes : 0u);
 #pragma unroll
       for (int p = 0; p < P; p++) x[p] = load_in<Op, POL>(rx, voff[p]);
+      if constexpr (accumulates<Op>::value) {
+        if (j + 4 > n) load_old<Op, P, POL>(old, wo, voff);  // the last pass: input n-1 is y, or the x just asked for
+      }
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int p = 0; p < P; p++) {
@@ -1161,11 +1240,18 @@ __device__ __forceinline__ void chunk_body(char *outb, Inputs in, uint32_t n, ui
 #pragma unroll
       for (int p = 0; p < P; p++) acc[p] = Op::add(acc[p], x[p]);
     }
+  } else if constexpr (accumulates<Op>::value) {
+    load_old<Op, P, POL>(old, wo, voff);  // n == 0: out = p + (+0), or p + a zero of alpha's sign
   }
   before_store();
-  rsrc_t w = make_rsrc(outb + off, nbytes);
+  if constexpr (accumulates<Op>::value) {
 #pragma unroll
-  for (int p = 0; p < P; p++) store_pkt<POL>(w, voff[p], pack_fin<Op>(acc[p], fin));
+    for (int p = 0; p < P; p++) store_pkt<POL>(wo, voff[p], Op::pack(acc[p], fin, old[p]));
+  } else {
+    rsrc_t w = make_rsrc(outb + off, nbytes);
+#pragma unroll
+    for (int p = 0; p < P; p++) store_pkt<POL>(w, voff[p], pack_fin<Op>(acc[p], fin));
+  }
 }
 
 // Engines: kTile = all n inputs of a BLOCK*U tile loaded together (small
@@ -1649,6 +1735,7 @@ constexpr int kPartProd = 2;  // PROD, BAND, BOR, BXOR
 constexpr int kPartScale = 3;  // post-scaled sums (kOpScaledSum)
 constexpr int kPartF8 = 4;  // the OCP FP8 types, every operator they have
 constexpr int kPartWiden = 5;  // widened sums (kOpWidenSum): 2-byte and FP8 inputs, f32 output
+constexpr int kPartAccum = 6;  // accumulating widened sums (kOpWidenAccum): out += alpha * sum
 
 // MAX and MIN of the six arithmetic types; HICCL_BYTES has no operator.
 template <bool MAX, class R, class F>
@@ -1765,9 +1852,25 @@ R with_elem_widen(int dtype, int acc, R unknown, F f) {
   }
 }
 
+// Accumulating widened sums (kOpWidenAccum): the widened sums' list with the
+// accumulating ops.  Untuned.
+template <class R, class F>
+R with_elem_accum(int dtype, int acc, R unknown, F f) {
+  if (acc != HICCL_ACC_NATIVE) return unknown;
+  switch (dtype) {
+    case HICCL_BFLOAT16: return f(Elem<HICCL_BFLOAT16, OpBF16AccF32, false>());
+    case HICCL_FLOAT16: return f(Elem<HICCL_FLOAT16, OpF16AccF32, false>());
+    case HICCL_FLOAT8_E4M3: return f(Elem<HICCL_FLOAT8_E4M3, OpF8AccF32<kE4M3>, false>());
+    case HICCL_FLOAT8_E5M2: return f(Elem<HICCL_FLOAT8_E5M2, OpF8AccF32<kE5M2>, false>());
+    default: return unknown;
+  }
+}
+
 template <int PART, class R, class F>
 R with_elem(int dtype, int acc, int op, R unknown, F f) {
-  if constexpr (PART == kPartWiden) {
+  if constexpr (PART == kPartAccum) {
+    return op == kOpWidenAccum ? with_elem_accum(dtype, acc, unknown, f) : unknown;
+  } else if constexpr (PART == kPartWiden) {
     return op == kOpWidenSum ? with_elem_widen(dtype, acc, unknown, f) : unknown;
   } else if constexpr (PART == kPartF8) {
     return with_elem_f8(dtype, acc, op, unknown, f);
@@ -1801,7 +1904,9 @@ R with_elem(int dtype, int acc, int op, R unknown, F f) {
 // registers (int32: exact, so it may) -- then 8.  The chunk is a property of
 // (dtype, acc): int32 takes 8 under every operator, so the host sizes a plan's
 // units without asking for the operator.
-// An int32 op says so itself (kHalfChunk).
+// An int32 op says so itself (kHalfChunk), and so does an accumulating widened
+// op (OpWidenAccum: the old output's packets are live next to the accumulators),
+// the one case where the chunk depends on the operator: phase_p takes it.
 template <class Op, class = void>
 struct half_chunk : std::false_type {};
 template <class Op>

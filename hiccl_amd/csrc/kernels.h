@@ -31,7 +31,9 @@ constexpr int kDefPol = 11;  // nt loads, nt stores
 //         small to give every CU several phased chunks;
 //  phase  512 lanes x P packets (P = phase_p: 16, or 8 where the accumulator
 //         of a packet takes 8 VGPRs -- bf16 / f16 WIDE -- or the adds get
-//         reassociated: int32) -- 128 KiB per input per chunk (64 KiB at P = 8).
+//         reassociated: int32 -- or the old output's packets are held next
+//         to the accumulators: kOpWidenAccum) -- 128 KiB per input per chunk
+//         (64 KiB at P = 8).
 // Both: nt loads and nt stores, one workgroup per CU, grid-stride.  Plan
 // kernels run the TILE engine at kDefBlock lanes only.
 constexpr int kDefBlock = 256;
@@ -50,6 +52,12 @@ constexpr int kOpScaledSum = 0x100;
 // elements).  Its kernels are the scaled ones' kind (they take a Scale): an
 // unscaled widened sum passes alpha = 1.
 constexpr int kOpWidenSum = 0x101;
+// An accumulating widened sum (hiccl_reduce_accumulate,
+// hiccl_reduce_plan_set_accumulate): a widened sum whose kernels read the old
+// f32 output and add the (scaled) sum to it.  Everything said of kOpWidenSum
+// holds; is_widen_op answers for both.
+constexpr int kOpWidenAccum = 0x102;
+constexpr bool is_widen_op(int op) { return op == kOpWidenSum || op == kOpWidenAccum; }
 
 // The scale of a scaled sum: alpha as the caller gave it (f64 kernels) and
 // rounded to nearest even to f32 (every other type).  The scaled kernels take
@@ -164,7 +172,11 @@ struct ProgArgs {
 size_t esize(int dtype);            // bytes per element, 0 for an unknown dtype
 // a headline type (f32, bf16 / f16 native) under SUM: the full tuning table
 bool tuned_type(int dtype, int acc, int op);
-int phase_p(int dtype, int acc);    // packets per lane of the PHASE engine's default chunk (any op)
+// packets per lane of the PHASE engine's default chunk: a property of (dtype,
+// acc) under every operator but kOpWidenAccum, which takes 8.  The operator is
+// not defaulted: a caller that sizes units (unit_pkts) must name the launch's
+// own, or the descriptor table and the kernel disagree about the chunk.
+int phase_p(int dtype, int acc, int op);
 
 // ---- kernel tables: the launcher of a shape, or NULL where no kernel has it
 // (engine: HICCL_ENGINE_TILE / _PHASE; pol: 10*store + load)
@@ -195,6 +207,9 @@ prog_fn pick_prog_f8(int dtype, int op, int unroll);
 // the widened sums (reduce_widen.hip; op == kOpWidenSum, dtype: the inputs'): no program kernels
 single_fn pick_single_widen(int dtype, int acc, int op, int engine, int block, int unroll, int pol);
 plan_fn pick_plan_widen(int dtype, int acc, int op, int engine, int unroll, int pol);
+// the accumulating widened sums (reduce_accum.hip; op == kOpWidenAccum, dtype: the inputs'): no program kernels
+single_fn pick_single_accum(int dtype, int acc, int op, int engine, int block, int unroll, int pol);
+plan_fn pick_plan_accum(int dtype, int acc, int op, int engine, int unroll, int pol);
 
 // ---- the plain kernels
 

@@ -23,7 +23,7 @@ uint32_t log2u(int v) {
 // memory and run it as a one-compute plan.
 int reduce_via_table(int dtype, const Cfg &c, const Scale &scale, void *out, const void *const *in, int n,
                      size_t count, hipStream_t s) {
-  DescTable t((size_t)n, unit_pkts(c.engine, dtype, c.acc, c.unroll));
+  DescTable t((size_t)n, unit_pkts(c.engine, dtype, c.acc, c.unroll, c.op));
   t.add(out, in, (size_t)n, count, out_esize(dtype, c.op));
   const std::vector<char> host = t.image();
   char *dmem = nullptr;
@@ -91,11 +91,13 @@ int check_widened(int in_dtype, int out_dtype, int acc, const double *alpha, con
 }
 
 // hiccl_reduce_op (scale NULL: `op` is a hiccl_op_t the caller has checked),
-// hiccl_reduce_scaled (op == kOpScaledSum) and hiccl_reduce_widened (op ==
-// kOpWidenSum: `dtype` is the inputs', the output is f32).
+// hiccl_reduce_scaled (op == kOpScaledSum), hiccl_reduce_widened (op ==
+// kOpWidenSum: `dtype` is the inputs', the output is f32) and
+// hiccl_reduce_accumulate (op == kOpWidenAccum: the same, and the kernels add
+// to the output).
 int reduce_call(int dtype, int op, const Scale *scale, void *out, const void *const *in, int n, size_t count,
                 void *stream, const hiccl_reduce_config_t *cfg) {
-  const bool widened = op == kOpWidenSum;
+  const bool widened = is_widen_op(op);
   const size_t esz = out_esize(dtype, op);  // of the OUTPUT: the split, the packets and the bytes written are its
   const Scale sc = scale ? *scale : Scale{0.0, 0.0f, 0u};
   if (widened) {
@@ -205,6 +207,22 @@ int hiccl_reduce_widened(int in_dtype, int out_dtype, const double *alpha, void 
   if (int e = check_widened(in_dtype, out_dtype, cfg ? cfg->acc : HICCL_ACC_NATIVE, alpha, "hiccl_reduce_widened", &sc))
     return e;
   return reduce_call(in_dtype, kOpWidenSum, &sc, out, in, n, count, stream, cfg);
+}
+
+int hiccl_reduce_accumulate(int in_dtype, int out_dtype, const double *alpha, void *out, const void *const *in, int n,
+                            size_t count, void *stream, const hiccl_reduce_config_t *cfg) {
+  Scale sc;
+  if (int e = check_widened(in_dtype, out_dtype, cfg ? cfg->acc : HICCL_ACC_NATIVE, alpha, "hiccl_reduce_accumulate", &sc))
+    return e;
+  return reduce_call(in_dtype, kOpWidenAccum, &sc, out, in, n, count, stream, cfg);
+}
+
+int hiccl_reduce_auto_choice_accumulate(int in_dtype, const hiccl_reduce_config_t *cfg, size_t count, double n, int cus,
+                                        int *engine, int *unroll, int *blocks_per_cu, int *dynamic, int *store_policy) {
+  if (int e = check_widened(in_dtype, HICCL_FLOAT32, cfg ? cfg->acc : HICCL_ACC_NATIVE, nullptr,
+                            "auto_choice_accumulate", nullptr))
+    return e;
+  return auto_choice(in_dtype, kOpWidenAccum, cfg, count, n, cus, engine, unroll, blocks_per_cu, dynamic, store_policy);
 }
 
 int hiccl_reduce_auto_choice_widened(int in_dtype, const hiccl_reduce_config_t *cfg, size_t count, double n, int cus,

@@ -126,7 +126,7 @@ int plan_upload(hiccl_reduce_plan *p, hipStream_t s) {
   p->engine = c.engine;
   p->unroll = c.unroll;
   p->bpc = c.bpc;
-  DescTable t(maxn, unit_pkts(p->engine, p->dtype, c.acc, p->unroll));
+  DescTable t(maxn, unit_pkts(p->engine, p->dtype, c.acc, p->unroll, c.op));
   for (auto &cp : p->comps) t.add(cp.out, cp.in.data(), cp.in.size(), cp.count, p->osz);
   const std::vector<char> host = t.image();
   if (int e = check_hip(hipMalloc((void **)&p->d_block, host.size()), "plan: hipMalloc")) return e;
@@ -178,7 +178,7 @@ int plan_set_field(hiccl_reduce_plan_t *p, int hiccl_reduce_config_t::*field, in
 }
 
 // Does every engine config `c` may resolve to have a plan kernel of operator
-// `op` (a hiccl_op_t, kOpScaledSum or kOpWidenSum) in the shape `c` names?  Empty string if
+// `op` (a hiccl_op_t, kOpScaledSum, kOpWidenSum or kOpWidenAccum) in the shape `c` names?  Empty string if
 // so, else why not.  No device work.
 std::string plan_config_error(const hiccl_reduce_plan *p, const hiccl_reduce_config_t &c, int op) {
   Cfg r = resolve(&c);
@@ -191,7 +191,7 @@ std::string plan_config_error(const hiccl_reduce_plan *p, const hiccl_reduce_con
     Cfg t = r;
     t.engine = eng;
     if (!t.block) t.block = eng == HICCL_ENGINE_PHASE ? kPhBlock : kDefBlock;
-    if (!t.unroll) t.unroll = eng == HICCL_ENGINE_PHASE ? phase_p(p->dtype, t.acc) : kDefUnroll;
+    if (!t.unroll) t.unroll = eng == HICCL_ENGINE_PHASE ? phase_p(p->dtype, t.acc, t.op) : kDefUnroll;
     const std::string why = plan_shape_error(t, p->dtype);
     if (!why.empty()) return why;
   }
@@ -249,7 +249,7 @@ int hiccl_reduce_plan_set_scale(hiccl_reduce_plan_t *p, const double *alpha) {
       return fail(hipErrorInvalidValue, "plan_set_scale: only sums are scaled (the plan's op is not HICCL_OP_SUM)");
     // the scaled kernels are untuned: a config that names a shape only the
     // tuned sums have (TILE unroll 1, 2, 8, 16) is refused here, not at launch
-    const std::string why = plan_config_error(p, p->req, p->widened ? kOpWidenSum : kOpScaledSum);
+    const std::string why = plan_config_error(p, p->req, p->widened ? p->kernel_op() : kOpScaledSum);
     if (!why.empty())
       return fail(hipErrorInvalidValue, "plan_set_scale: the plan's config names a shape the scaled kernels lack: " + why);
   }
@@ -287,6 +287,36 @@ int hiccl_reduce_plan_set_out_dtype(hiccl_reduce_plan_t *p, int out_dtype) {
   return 0;
 }
 
+int hiccl_reduce_plan_set_accumulate(hiccl_reduce_plan_t *p, int on) {
+  if (!p) return fail(hipErrorInvalidValue, "plan_set_accumulate: plan is NULL");
+  if (on) {
+    if (!p->widened)
+      return fail(hipErrorInvalidValue, "plan_set_accumulate: only a widened plan accumulates (hiccl_reduce_plan_set_out_dtype "
+                                        "first): a same-type sum accumulates by passing out as input 0");
+    if (p->peer & HICCL_PEER_STORES)
+      return fail(hipErrorInvalidValue, "plan_set_accumulate: an accumulating plan takes no HICCL_PEER_STORES (the old output "
+                                        "is read where it is written: keep it in local memory)");
+    // the accumulating kernels are untuned, as the widened ones: the same shapes
+    const std::string why = plan_config_error(p, p->req, kOpWidenAccum);
+    if (!why.empty())
+      return fail(hipErrorInvalidValue,
+                  "plan_set_accumulate: the plan's config names a shape the accumulating kernels lack: " + why);
+  } else if (p->accumulate) {
+    // back to the widened kernels, whose PHASE shape is not the accumulating
+    // ones': a config that names the latter is refused here, not replaced
+    const std::string why = plan_config_error(p, p->req, kOpWidenSum);
+    if (!why.empty())
+      return fail(hipErrorInvalidValue,
+                  "plan_set_accumulate: the plan's config names a shape the widened kernels lack: " + why);
+  }
+  // another kernel: the next launch uploads again (a new alpha alone does not)
+  if (p->accumulate != (on != 0)) p->dirty = true;
+  p->accumulate = on != 0;
+  return 0;
+}
+
+int hiccl_reduce_plan_accumulate(const hiccl_reduce_plan_t *p) { return !p ? -1 : p->accumulate ? 1 : 0; }
+
 int hiccl_reduce_plan_out_dtype(const hiccl_reduce_plan_t *p) {
   return !p ? -1 : p->widened ? (int)HICCL_FLOAT32 : p->dtype;
 }
@@ -299,6 +329,9 @@ int hiccl_reduce_plan_set_peer(hiccl_reduce_plan_t *p, int flags) {
   if (!p) return fail(hipErrorInvalidValue, "plan_set_peer: plan is NULL");
   if (flags & ~(HICCL_PEER_STORES | HICCL_PEER_LOADS))
     return fail(hipErrorInvalidValue, "plan_set_peer: flags must be a combination of HICCL_PEER_STORES and HICCL_PEER_LOADS");
+  if (p->accumulate && (flags & HICCL_PEER_STORES))
+    return fail(hipErrorInvalidValue, "plan_set_peer: an accumulating plan takes no HICCL_PEER_STORES (the old output is "
+                                      "read where it is written: keep it in local memory)");
   p->peer = flags;
   p->dirty = true;
   return 0;
@@ -420,7 +453,9 @@ void *hiccl_reduce_plan_stream(hiccl_reduce_plan_t *p) {
 size_t hiccl_reduce_plan_bytes(const hiccl_reduce_plan_t *p) {
   if (!p) return 0;
   size_t b = 0;
-  for (auto &c : p->comps) b += c.count * (c.in.size() * p->esz + p->osz);
+  // an accumulating plan reads the old output and writes the new one
+  const size_t obytes = p->accumulate ? 2 * p->osz : p->osz;
+  for (auto &c : p->comps) b += c.count * (c.in.size() * p->esz + obytes);
   return b;
 }
 

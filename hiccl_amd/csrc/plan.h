@@ -16,7 +16,11 @@ struct hiccl_reduce_plan {
   hiccl_impl::Scale scale{0.0, 0.0f, 0u};
   bool widened = false;           // hiccl_reduce_plan_set_out_dtype: dtype inputs, f32 outputs (op stays SUM)
   // the operator the policy and the kernel tables see
-  int kernel_op() const { return widened ? hiccl_impl::kOpWidenSum : scaled ? hiccl_impl::kOpScaledSum : op; }
+  bool accumulate = false;        // hiccl_reduce_plan_set_accumulate: out += (alpha *) sum, on a widened plan only
+  int kernel_op() const {
+    return widened ? (accumulate ? hiccl_impl::kOpWidenAccum : hiccl_impl::kOpWidenSum)
+                   : scaled ? hiccl_impl::kOpScaledSum : op;
+  }
   // the scale a launch carries: a widened plan's kernels always multiply (by one if unscaled)
   hiccl_impl::Scale kernel_scale() const { return widened && !scaled ? hiccl_impl::Scale{1.0, 1.0f, 0u} : scale; }
   bool has_scale() const { return scaled || widened; }

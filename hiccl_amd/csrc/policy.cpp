@@ -35,6 +35,15 @@
 // 2-byte or FP8 accumulator is the 16 the widened ops have -- and the store
 // form follows the bytes written.  No threshold below has been measured for
 // it; DESIGN.md section 5 (M22) records the one measurement.
+//
+// An accumulating widened sum (kOpWidenAccum) takes the widened sum's rules
+// word for word: the same packets, the same bytes written, and the widened
+// sum's 16-packet chunk in every threshold (auto_engine, auto_bpc), so it
+// answers what the widened sum answers.  Only the shape its PHASE kernels run
+// differs: 8 packets per lane (phase_p with the operator: finish_cfg,
+// unit_pkts, plan_shape_error).  It reads 4 more bytes per element (the old
+// output), which no rule counts.  No AUTO threshold of its own; DESIGN.md
+// section 5 (M23).
 #include "policy.h"
 
 namespace hiccl_impl {
@@ -75,6 +84,13 @@ inline uint64_t wt_cap(double n) { return n >= 1.5 ? kWtMaxBytesReduce : kWtMaxB
 
 // The paced one-shot tiles' share of the default grid (launch_shape).
 constexpr uint64_t kPacedGridNum = 7, kPacedGridDen = 8;
+
+// The operator AUTO's thresholds are counted for: an accumulating widened sum
+// takes the widened sum's, on purpose -- the same chunk (16 packets) in every
+// threshold, so both sums resolve to the same engine, grid and store form, and
+// only the shape its PHASE kernels run differs (phase_p with the launch's own
+// operator: finish_cfg, unit_pkts, plan_shape_error).
+inline int threshold_op(int op) { return op == kOpWidenAccum ? kOpWidenSum : op; }
 
 constexpr int kDefBpc = 1;
 constexpr int kSmallBpc = 4;
@@ -134,7 +150,7 @@ int auto_engine(uint64_t npkt, double n, int dtype, const Cfg &c, int dev) {
     const uint64_t tickets = npkt / ((uint64_t)kDefBlock * kDefUnroll) / default_grab(HICCL_ENGINE_TILE, n);
     if (tickets >= kTileMinTicketsPerWG * (uint64_t)device_cus(dev)) return HICCL_ENGINE_TILE;
   }
-  const uint64_t chunk = (uint64_t)kPhBlock * phase_p(dtype, acc);
+  const uint64_t chunk = (uint64_t)kPhBlock * phase_p(dtype, acc, threshold_op(c.op));
   const uint64_t cus = (uint64_t)device_cus(dev);
   const uint64_t per_cu = npkt / (cus * chunk);  // phased chunks per CU
   // Round 3, on the round-2 kernels (interleaved one-shot sweeps of n = 2 /
@@ -177,8 +193,8 @@ int auto_engine(uint64_t npkt, double n, int dtype, const Cfg &c, int dev) {
 // few tiles per workgroup and is latency-bound -- four workgroups per CU
 // keep more of it in flight (n = 8, 16 MiB per input: 6.31 vs 6.01 TB/s,
 // 32 MiB: 6.27-6.40 vs 5.97-6.13; profiles/r01g_small_sweep.jsonl).
-int auto_bpc(int engine, uint64_t npkt, int dtype, int acc, int dev) {
-  const uint64_t chunk = (uint64_t)kPhBlock * phase_p(dtype, acc);
+int auto_bpc(int engine, uint64_t npkt, int dtype, int acc, int op, int dev) {
+  const uint64_t chunk = (uint64_t)kPhBlock * phase_p(dtype, acc, threshold_op(op));
   return engine == HICCL_ENGINE_TILE && npkt < kPhaseMinChunksPerCU * (uint64_t)device_cus(dev) * chunk
              ? kSmallBpc
              : kDefBpc;
@@ -293,7 +309,7 @@ void finish_cfg(Cfg &c, uint64_t npkt, double n, int dtype, int dev) {
     c.engine = (c.block || c.unroll) ? HICCL_ENGINE_TILE : auto_engine(npkt, n, dtype, c, dev);
   if (c.engine == HICCL_ENGINE_PHASE) {
     if (!c.block) c.block = kPhBlock;
-    if (!c.unroll) c.unroll = phase_p(dtype, c.acc);
+    if (!c.unroll) c.unroll = phase_p(dtype, c.acc, c.op);
   } else {
     if (!c.block) c.block = kDefBlock;
     if (!c.unroll) {
@@ -301,7 +317,7 @@ void finish_cfg(Cfg &c, uint64_t npkt, double n, int dtype, int dev) {
       c.unroll = wide ? wide : auto_unroll(npkt, dtype, c, dev);
     }
   }
-  if (!c.bpc) c.bpc = auto_bpc(c.engine, npkt, dtype, c.acc, dev);
+  if (!c.bpc) c.bpc = auto_bpc(c.engine, npkt, dtype, c.acc, c.op, dev);
 }
 
 // The store form is decided first (wt_by_size), since AUTO's engine rules
@@ -333,8 +349,8 @@ int plan_pol(int peer) {
          ((peer & HICCL_PEER_LOADS) ? kPolLoadSys : kDefPol % 10);
 }
 
-uint64_t unit_pkts(int engine, int dtype, int acc, int unroll) {
-  return engine == HICCL_ENGINE_PHASE ? (uint64_t)kPhBlock * phase_p(dtype, acc)
+uint64_t unit_pkts(int engine, int dtype, int acc, int unroll, int op) {
+  return engine == HICCL_ENGINE_PHASE ? (uint64_t)kPhBlock * phase_p(dtype, acc, op)
                                       : (uint64_t)kDefBlock * (unroll ? unroll : kDefUnroll);
 }
 
@@ -345,9 +361,9 @@ std::string plan_shape_error(const Cfg &c, int dtype) {
   if (c.drain) return "plan kernels do not support drain";
   if (c.order != 0 && c.order != 1) return "plan kernels run their units in linear order (order 0)";
   if (c.engine == HICCL_ENGINE_PHASE) {
-    if (c.block != kPhBlock || c.unroll != phase_p(dtype, c.acc))
+    if (c.block != kPhBlock || c.unroll != phase_p(dtype, c.acc, c.op))
       return "plan kernels run the PHASE engine in its default shape only (block 512, unroll " +
-             std::to_string(phase_p(dtype, c.acc)) + ")";
+             std::to_string(phase_p(dtype, c.acc, c.op)) + ")";
     return "";
   }
   if (c.block != kDefBlock) return "plan kernels run the TILE engine at block 256 only";

@@ -15,7 +15,7 @@ struct Cfg {
   bool wt;          // the launch stores write-through by size: decided BEFORE the engine
                     // (oneshot_cfg, plan_cfg), since AUTO's engine rules differ under it
   int order;        // tile-order segments (hiccl_reduce_config_t.order; 0/1 linear)
-  int op;           // hiccl_op_t, or kOpScaledSum (a scaled sum: untuned, like every operator but
+  int op;           // hiccl_op_t, kOpWidenSum / kOpWidenAccum, or kOpScaledSum (a scaled sum: untuned, like every operator but
                     // SUM, and honours acc): not a config entry -- the call or the plan names it
                     // (resolve: SUM)
   int pol() const { return store * 10 + nt; }
@@ -44,11 +44,13 @@ int check_scale(int dtype, double alpha, const std::string &who, Scale *scale);
 // likewise; *scale (may be NULL): the kernels' argument.
 bool widen_in_dtype(int dtype);
 int check_widened(int in_dtype, int out_dtype, int acc, const double *alpha, const std::string &who, Scale *scale);
-// Bytes per element a call writes: 4 for a widened sum, else the dtype's.
-inline size_t out_esize(int dtype, int op) { return op == kOpWidenSum ? 4 : esize(dtype); }
+// Bytes per element a call writes: 4 for a widened sum (accumulating or not),
+// else the dtype's.
+inline size_t out_esize(int dtype, int op) { return is_widen_op(op) ? 4 : esize(dtype); }
 // The one-shot call behind hiccl_reduce_op (scale NULL, `op` checked by the
 // caller), hiccl_reduce_scaled (op kOpScaledSum) and hiccl_reduce_widened (op
-// kOpWidenSum, dtype the inputs', scale never NULL): oneshot.cpp.
+// kOpWidenSum, dtype the inputs', scale never NULL) and hiccl_reduce_accumulate
+// (op kOpWidenAccum, likewise): oneshot.cpp.
 int reduce_call(int dtype, int op, const Scale *scale, void *out, const void *const *in, int n, size_t count,
                 void *stream, const hiccl_reduce_config_t *cfg);
 
@@ -74,7 +76,7 @@ inline single_fn single_for(int dtype, const Cfg &c) {
 // policy (HICCL_PEER_* flags: system-scope stores and/or loads).
 int plan_pol(int peer);
 // Packets per work unit (tile or chunk) of a plan kernel.
-uint64_t unit_pkts(int engine, int dtype, int acc, int unroll);
+uint64_t unit_pkts(int engine, int dtype, int acc, int unroll, int op);
 // Is `c` (engine resolved, shape filled in by finish_cfg) a shape the plan
 // kernels have?  Empty string if so, else why not.
 std::string plan_shape_error(const Cfg &c, int dtype);

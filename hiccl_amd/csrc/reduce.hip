@@ -168,7 +168,8 @@ bool tuned_type(int dtype, int acc, int op) {
   return part_tuned<kPartSum>(dtype, acc, op);
 }
 
-int phase_p(int dtype, int acc) {
+int phase_p(int dtype, int acc, int op) {
+  if (op == kOpWidenAccum) return phase_p_of<OpBF16AccF32>();  // the four accumulating ops alike
   if (is_f8(dtype)) return acc == HICCL_ACC_WIDE ? phase_p_of<OpF8Wide<kE4M3>>() : phase_p_of<OpF8<kE4M3>>();
   return with_elem_sum(dtype, acc, 16, [](auto e) { return phase_p_of<typename decltype(e)::Op>(); });
 }
@@ -177,8 +178,9 @@ int phase_p(int dtype, int acc) {
 // and the bitwise operators from reduce_prod.hip, the scaled sums from
 // reduce_scale.hip; the FP8 types' kernels, whatever the operator, from
 // reduce_f8.hip; the widened sums (whose dtype is the inputs') from
-// reduce_widen.hip.
+// reduce_widen.hip, the accumulating ones from reduce_accum.hip.
 single_fn pick_single(int dtype, int acc, int op, int engine, int block, int unroll, int pol) {
+  if (op == kOpWidenAccum) return pick_single_accum(dtype, acc, op, engine, block, unroll, pol);
   if (op == kOpWidenSum) return pick_single_widen(dtype, acc, op, engine, block, unroll, pol);
   if (is_f8(dtype)) return pick_single_f8(dtype, acc, op, engine, block, unroll, pol);
   if (op == kOpScaledSum) return pick_single_scale(dtype, acc, op, engine, block, unroll, pol);
@@ -188,6 +190,7 @@ single_fn pick_single(int dtype, int acc, int op, int engine, int block, int unr
 }
 
 plan_fn pick_plan(int dtype, int acc, int op, int engine, int unroll, int pol) {
+  if (op == kOpWidenAccum) return pick_plan_accum(dtype, acc, op, engine, unroll, pol);
   if (op == kOpWidenSum) return pick_plan_widen(dtype, acc, op, engine, unroll, pol);
   if (is_f8(dtype)) return pick_plan_f8(dtype, acc, op, engine, unroll, pol);
   if (op == kOpScaledSum) return pick_plan_scale(dtype, acc, op, engine, unroll, pol);
@@ -197,7 +200,7 @@ plan_fn pick_plan(int dtype, int acc, int op, int engine, int unroll, int pol) {
 }
 
 prog_fn pick_prog(int dtype, int op, int unroll) {
-  if (op == kOpWidenSum) return nullptr;  // no program runs a widened plan (hiccl_program_add_plan)
+  if (is_widen_op(op)) return nullptr;  // no program runs a widened plan (hiccl_program_add_plan)
   if (is_f8(dtype)) return pick_prog_f8(dtype, op, unroll);
   if (op >= HICCL_OP_PROD) return pick_prog_prod(dtype, op, unroll);
   if (op != HICCL_OP_SUM) return pick_prog_maxmin(dtype, op, unroll);

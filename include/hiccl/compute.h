@@ -302,6 +302,9 @@ class Compute {
 // master gradients in one pass).  set_scale multiplies once in f32 at store
 // time.  An output may not overlap an input.  The host port does the same
 // arithmetic in plain C++ (widen_sum, elem_types.h): the same bits.
+// set_accumulate makes every start() ADD to the outputs instead of overwriting
+// them (hiccl_reduce_plan_set_accumulate): out = fl32(out + r), r the finished
+// (and scaled) sum -- an f32 master gradient accumulated over micro-batches.
 // A Comm<T> schedule has no use for it (a schedule moves T between ranks, and
 // a widened sum changes type inside the tree: INTEGRATION.md).
 template <typename T>
@@ -340,6 +343,7 @@ class WidenCompute {
       }
       check(hiccl_reduce_plan_set_out_dtype(plan, HICCL_FLOAT32), "plan_set_out_dtype");  // before the first add
       if (scaled) check(hiccl_reduce_plan_set_scale(plan, &scale), "plan_set_scale");
+      if (accumulating) check(hiccl_reduce_plan_set_accumulate(plan, 1), "plan_set_accumulate");
     }
     if (peer_inputs && !(hiccl_reduce_plan_peer(plan) & HICCL_PEER_LOADS))
       check(hiccl_reduce_plan_set_peer(plan, hiccl_reduce_plan_peer(plan) | HICCL_PEER_LOADS), "plan_set_peer");
@@ -365,6 +369,15 @@ class WidenCompute {
 #endif
   }
 
+  // out = fl32(out + r) from the next start() on, r the sum (times the scale):
+  // every start() accumulates once more.  At any time; false: overwrite again.
+  void set_accumulate(bool on = true) {
+    accumulating = on;
+#ifndef HICCL_PORT_HOST
+    if (plan) check(hiccl_reduce_plan_set_accumulate(plan, on ? 1 : 0), "plan_set_accumulate");
+#endif
+  }
+
   void start() {
     if (!numcomp) return;
 #ifndef HICCL_PORT_HOST
@@ -375,8 +388,18 @@ class WidenCompute {
       T *const *in = inputbuf[c].data();
       const int k = (int)inputbuf[c].size();
       const size_t n = count[c];
+      if (accumulating) {
 #pragma omp parallel for schedule(static)
-      for (size_t i = 0; i < n; i++) out[i] = widen_sum<T>(in, k, i, scaled, scale);
+        for (size_t i = 0; i < n; i++) {
+          // r in a statement of its own (and volatile, as widen_sum's partial
+          // sums): a contracting compiler cannot fuse the multiply with the add
+          volatile float r = widen_sum<T>(in, k, i, scaled, scale);
+          out[i] = out[i] + r;
+        }
+      } else {
+#pragma omp parallel for schedule(static)
+        for (size_t i = 0; i < n; i++) out[i] = widen_sum<T>(in, k, i, scaled, scale);
+      }
     }
 #endif
   }
@@ -387,10 +410,12 @@ class WidenCompute {
 #endif
   }
 
-  // Algorithmic bytes of one start(): sum of count * (n * sizeof(T) + 4).
+  // Algorithmic bytes of one start(): sum of count * (n * sizeof(T) + 4); an
+  // accumulating compute also reads its output: + 8.
   size_t bytes() const {
+    const size_t obytes = accumulating ? 2 * sizeof(float) : sizeof(float);
     size_t b = 0;
-    for (int c = 0; c < numcomp; c++) b += count[c] * (inputbuf[c].size() * sizeof(T) + sizeof(float));
+    for (int c = 0; c < numcomp; c++) b += count[c] * (inputbuf[c].size() * sizeof(T) + obytes);
     return b;
   }
 
@@ -409,7 +434,7 @@ class WidenCompute {
   }
 
   // Compute<T>::measure(warmup, numiter), pricing n * sizeof(T) + 4 bytes per
-  // element, summed over ranks; the roofline line prices the busiest rank.
+  // element (+ 8 when accumulating: bytes()), summed over ranks; the roofline line prices the busiest rank.
   void measure(int warmup, int numiter) {
     report();
     unsigned long busiest = (unsigned long)bytes(), tot = (unsigned long)bytes();
@@ -444,6 +469,7 @@ class WidenCompute {
  private:
   bool scaled = false;
   double scale = 1.0;
+  bool accumulating = false;  // set_accumulate
 #ifndef HICCL_PORT_HOST
   hiccl_reduce_plan_t *plan = nullptr;
   static void check(int e, const char *what) {

@@ -354,6 +354,42 @@ int hiccl_reduce_auto_choice_widened(int in_dtype, const hiccl_reduce_config_t *
                                      int *store_policy);
 
 /* ----------------------------------------------------------------------
+ * Accumulating widened sums: out += alpha * sum -- an f32 master-gradient
+ * buffer accumulated across micro-batches, buckets or the partial results of a
+ * reduce tree, in the widened sum's own pass and with no f32 temporary.
+ * Everything hiccl_reduce_widened says holds (dtypes, alpha, buffer rules, the
+ * layout, the store-form rule on the 4 * count bytes written, n > 64 on the
+ * plan kernel, n <= 64 capturable), and the kernels' shapes but one: PHASE's
+ * default chunk is 8 packets per lane here (16,384 elements; a config that
+ * names the widened sums' 16 is refused).  The difference is the last step.
+ * With p = out[i] as it was BEFORE the launch:
+ *
+ *   s32     hiccl_reduce_widened's s32[i], finished first: p is not addend 0
+ *   r       s32 (alpha == NULL), or fl32(s32 * a32), a32 = (float)*alpha
+ *   out[i]  fl32(p + r)
+ *
+ * Three separately rounded f32 operations, never a fused multiply-add; the
+ * scale applies to the new contribution only.  Subnormals are kept, Inf + -Inf
+ * is NaN, NaNs compare by NaN-ness, nothing is clamped.  n == 0 gives
+ * fl32(p + (+0)), scaled p + a zero with alpha's sign: p is kept, except that
+ * -0 + +0 is +0.  count == 0 is a no-op.  The unscaled form runs the scaled
+ * kernels with a32 = 1.0f.
+ * EVERY LAUNCH ACCUMULATES: a second call, enqueue or graph replay adds r
+ * again, fl32(fl32(p + r) + r).  Every element is read, modified and written
+ * exactly once per launch.
+ * NO ALIASING, as for every widened sum: `out` may overlap no input.
+ * Not covered: a factor on the old output (beta), f32 / f64 inputs, narrowing
+ * outputs, the host pipe, programs, Comm<T>.
+ * hiccl_reduce_auto_choice_accumulate answers as hiccl_reduce_auto_choice_widened
+ * does, by the same rules and thresholds (none of its own); under PHASE its
+ * `unroll` says 8. */
+int hiccl_reduce_accumulate(int in_dtype, int out_dtype, const double *alpha, void *out, const void *const *in,
+                            int n, size_t count, void *stream, const hiccl_reduce_config_t *cfg);
+int hiccl_reduce_auto_choice_accumulate(int in_dtype, const hiccl_reduce_config_t *cfg, size_t count, double n,
+                                        int cus, int *engine, int *unroll, int *blocks_per_cu, int *dynamic,
+                                        int *store_policy);
+
+/* ----------------------------------------------------------------------
  * Persistent plan: the C-ABI counterpart of the reference's Compute<T>
  * (compute.h:26-204).  A plan holds any number of registered computes and
  * launches ALL of them in ONE kernel (one launch per pipeline step instead
@@ -431,6 +467,24 @@ int hiccl_reduce_plan_scale(const hiccl_reduce_plan_t *plan, double *alpha);
  * widened), -1 for NULL. */
 int hiccl_reduce_plan_set_out_dtype(hiccl_reduce_plan_t *plan, int out_dtype);
 int hiccl_reduce_plan_out_dtype(const hiccl_reduce_plan_t *plan);
+/* Accumulation (hiccl_reduce_accumulate): with `on` non-zero every compute of a
+ * WIDENED plan writes out + (alpha *) sum from the next launch on, launch_each
+ * included; 0 goes back to overwriting.  May be called at any time, like
+ * set_scale: a switch re-uploads at the next launch (the kernel differs), a new
+ * alpha alone does not.  Every launch, enqueue, launch_each and graph replay
+ * accumulates once more.  Refused, before any device work: a plan that is not
+ * widened, a plan with HICCL_PEER_STORES (and set_peer refuses that flag on an
+ * accumulating plan: the old output would be read from a peer's memory;
+ * HICCL_PEER_LOADS -- inputs in a peer's memory, the output local -- is taken),
+ * and, in either direction, a config whose shape the kernels about to run
+ * lack: the PHASE shape is 512 x 8 for the accumulating kernels and 512 x 16
+ * for the widened ones, so a config that names one of them is refused by the
+ * switch to the other (the plan stays as it was; AUTO and TILE configs switch
+ * freely).  hiccl_reduce_plan_bytes prices
+ * count * (n * esz + 8) per compute; hiccl_program_add_plan keeps refusing the
+ * plan.  hiccl_reduce_plan_accumulate: 1 / 0, -1 for NULL. */
+int hiccl_reduce_plan_set_accumulate(hiccl_reduce_plan_t *plan, int on);
+int hiccl_reduce_plan_accumulate(const hiccl_reduce_plan_t *plan);
 /* Engine for the plan's launches (hiccl_engine_t; default AUTO, decided from
  * the total packets of all computes at the first launch after an add). */
 int hiccl_reduce_plan_set_engine(hiccl_reduce_plan_t *plan, int engine);

@@ -5,10 +5,12 @@ bench.py (`--nway`, `--chunks`, `--roundtrip`, `--c3vsc2`, `--progstep`).
 They share bench.py's buckets, timers and ceilings (imported as `B`) and
 print one JSON line per case; the driver's line is bench.py's default run.
 
-`widen` (the widened sums against the convert-then-reduce path) is not one of
-bench.py's flags; it runs from here:
+`widen` (the widened sums against the convert-then-reduce path) and `accum` (the
+accumulating widened sums against the two-pass path) are not among bench.py's
+flags; they run from here:
 
     python tools/bench_modes.py widen [--steps K] [--warmup W] [--rounds R] [--log2count L]
+    python tools/bench_modes.py accum [--steps K] [--warmup W] [--rounds R] [--log2count L]
 """
 import ctypes
 import json
@@ -460,13 +462,78 @@ def widen(args):
     return 0
 
 
+def accum(args):
+    """Accumulating widened sums on config 2's element count: out += sum of
+    8 x 2^28 bf16 / f16 / e4m3 / e5m2 inputs, the output f32, under AUTO.  Three
+    legs per type, alternating within this process for `--rounds` rounds of
+    `--steps` launches timed by device events:
+      accumulate    hiccl_amd.reduce_widened(accumulate=True), one kernel:
+                    count * (n * esz + 8) bytes;
+      two_pass      what a caller had without it: reduce_widened into an f32
+                    temporary, then hiccl_amd.reduce(out, [out, tmp]) in f32 (the
+                    events enclose both kernels): count * (n * esz + 16) bytes and
+                    the temporary;
+      widened       the plain widened sum, which overwrites: count * (n * esz + 4).
+    One JSON line per type.  Before anything is timed one accumulate launch is
+    compared with one two-pass round from the same prior (which holds no -0) on
+    a sample of 2^20 words, bit for bit."""
+    n, count = 8, 1 << getattr(args, "log2count", 28)
+    rounds = getattr(args, "rounds", 5)
+    for name, dtype in (("bf16", torch.bfloat16), ("f16", torch.float16), ("e4m3", torch.float8_e4m3fn),
+                        ("e5m2", torch.float8_e5m2)):
+        esz = torch.empty((), dtype=dtype).element_size()
+        ins, _ = B.make_bucket(n, count, dtype)
+        out = torch.empty(count, dtype=torch.float32, device="cuda")
+        out2 = torch.empty(count, dtype=torch.float32, device="cuda")
+        tmp = torch.empty(count, dtype=torch.float32, device="cuda")
+        hiccl_amd.fill_uniform(out, seed=23, k=1)
+        out2.copy_(out)
+
+        def two_pass():
+            hiccl_amd.reduce_widened(tmp, ins)
+            hiccl_amd.reduce(out2, [out2, tmp])
+
+        legs = {
+            "accumulate": lambda: hiccl_amd.reduce_widened(out, ins, accumulate=True),
+            "two_pass": two_pass,
+            "widened": lambda: hiccl_amd.reduce_widened(tmp, ins),
+        }
+        legs["accumulate"]()
+        legs["two_pass"]()
+        torch.cuda.synchronize()
+        sample = slice(0, min(count, 1 << 20))
+        exact = bool(torch.equal(out[sample].view(torch.int32), out2[sample].view(torch.int32)))
+        ms = {k: [] for k in legs}
+        for _ in range(rounds):
+            for k, fn in legs.items():
+                _, t = B.time_launches(fn, args.steps, args.warmup)
+                ms[k].append(float(np.median(t)))
+        med = {k: float(np.median(v)) for k, v in ms.items()}
+        alg = {"accumulate": count * (n * esz + 8), "two_pass": count * (n * esz + 16), "widened": count * (n * esz + 4)}
+        row = {"mode": "accum", "in_dtype": name, "n": n, "count": count, "rounds": rounds, "steps": args.steps,
+               "auto_choice": hiccl_amd.auto_choice(dtype, count, n, out_dtype=torch.float32, accumulate=True),
+               "bit_exact_vs_two_pass_sample": exact}
+        for k in legs:
+            row[k + "_ms"] = round(med[k], 4)
+            row[k + "_ms_per_round"] = [round(v, 4) for v in ms[k]]
+            row[k + "_bytes"] = alg[k]
+            row[k + "_GBps"] = round(alg[k] / (med[k] * 1e-3) / 1e9, 1)
+        row["accumulate_over_two_pass"] = round(med["accumulate"] / med["two_pass"], 4)
+        row["accumulate_over_widened"] = round(med["accumulate"] / med["widened"], 4)
+        row["device"] = torch.cuda.get_device_properties(0).name
+        print(json.dumps(row), flush=True)
+        del ins, out, out2, tmp
+        torch.cuda.empty_cache()
+    return 0
+
+
 if __name__ == "__main__":
     import argparse
     ap = argparse.ArgumentParser(description="modes that bench.py has no flag for")
-    ap.add_argument("mode", choices=["widen"])
+    ap.add_argument("mode", choices=["widen", "accum"])
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--log2count", type=int, default=28)
     a = ap.parse_args()
-    raise SystemExit(widen(a))
+    raise SystemExit(accum(a) if a.mode == "accum" else widen(a))
