@@ -18,8 +18,8 @@ $(PROBE): tools/hbm_probe.hip
 # (engine.h) -- reduce.hip, the SUM kernels, reduce_ops.hip, the MAX / MIN
 # kernels, reduce_prod.hip, the PROD and bitwise kernels, and reduce_scale.hip,
 # the scaled sums, which also takes in reduce_f8.hip, the OCP FP8 types, and
-# reduce_widen.hip, the widened sums, and reduce_accum.hip, the accumulating
-# ones (the library keeps four code objects, the
+# reduce_widen.hip, the widened sums, reduce_accum.hip, the accumulating
+# ones, and reduce_mixed.hip, the mixed plan kernels (the library keeps four code objects, the
 # scaled sums' last), compiled side by
 # side (reduce.hip the longest) -- and the host files (seconds each), as
 # objects under build/obj, linked once.  The link order is the order of the
@@ -83,7 +83,8 @@ CPP_BINS = build/plan_dump build/collectives_host build/collectives_host_f32 bui
            build/f8_add build/f8_compute_host build/f8_compute_hip \
            build/types_comm_host build/types_comm_hip \
            build/widen_sum build/widen_sum_hip \
-           build/accum_sum build/accum_sum_hip
+           build/accum_sum build/accum_sum_hip \
+           build/avg_comm_host build/avg_comm_hip
 
 cpp: $(CPP_BINS)
 
@@ -250,6 +251,16 @@ build/accum_sum: tests/cpp/accum_sum.cpp $(HDRS)
 	$(CXX) $(CXXFLAGS) -fopenmp -DHICCL_PORT_HOST -o $@ $< $(MPI_LINK)
 
 build/accum_sum_hip: tests/cpp/accum_sum.cpp $(HDRS) $(LIB)
+	@mkdir -p build
+	$(CXX) $(CXXFLAGS) $(HIP_HOST) -o $@ $< $(HIP_LINK) $(MPI_LINK)
+
+# Averaging Comm<T>: types_comm's driver with Comm<T>::set_scale(alpha) before
+# the collective is composed (tests/test_avg_comm_cpu.py, tests/test_avg_comm_gpu.py)
+build/avg_comm_host: tests/cpp/avg_comm.cpp $(HDRS)
+	@mkdir -p build
+	$(CXX) $(CXXFLAGS) -fopenmp -DHICCL_PORT_HOST -o $@ $< $(MPI_LINK)
+
+build/avg_comm_hip: tests/cpp/avg_comm.cpp $(HDRS) $(LIB)
 	@mkdir -p build
 	$(CXX) $(CXXFLAGS) $(HIP_HOST) -o $@ $< $(HIP_LINK) $(MPI_LINK)
 

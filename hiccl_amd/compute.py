@@ -469,15 +469,23 @@ class Compute:
             t, off = buf, 0
         return t, t.data_ptr() + off * esz
 
-    def add(self, inputbuf, outputbuf, count, compid):
+    def add(self, inputbuf, outputbuf, count, compid, unscaled=False):
+        """Register one compute on its owning rank.  ``unscaled``: in a plan
+        that has a scale this compute writes the plain sum
+        (hiccl_reduce_plan_add_unscaled: an intermediate compute of a
+        hierarchical average); without a scale it changes nothing.  A widened
+        or accumulating plan takes none."""
         if self.myid != compid:
             return
+        if unscaled and self.out_dtype != self.dtype:
+            raise ValueError("hiccl: a widened or accumulating plan takes no unscaled compute (one scale per plan)")
         esz = L.lib().hiccl_dtype_size(self.code)
         ins = [self._ptr(b, esz) for b in inputbuf]
         ot, op = self._ptr(outputbuf, L.lib().hiccl_dtype_size(L.DTYPE_OF_TORCH[self.out_dtype]))
         tab = _ptr_table([p for _, p in ins])
-        L.check(L.lib().hiccl_reduce_plan_add(self._plan, ctypes.c_void_p(op), tab, len(ins), count),
-                "plan_add")
+        fn = L.lib().hiccl_reduce_plan_add_unscaled if unscaled else L.lib().hiccl_reduce_plan_add
+        L.check(fn(self._plan, ctypes.c_void_p(op), tab, len(ins), count),
+                "plan_add_unscaled" if unscaled else "plan_add")
         if count == 0:  # validated, then dropped by the plan (a no-op): numcomp is hiccl_reduce_plan_numcomp
             return
         self._keep.append((ot, [t for t, _ in ins]))
@@ -485,6 +493,10 @@ class Compute:
         self.outputbuf.append(op)
         self.count.append(count)
         self.numcomp += 1
+
+    def num_unscaled(self):
+        """Computes added with ``unscaled=True`` (hiccl_reduce_plan_num_unscaled)."""
+        return L.lib().hiccl_reduce_plan_num_unscaled(self._plan)
 
     def stream_handle(self):
         """The plan's own stream (hipStream_t as int)."""

@@ -8,8 +8,9 @@
 // reduce_prod.hip for PROD and the bitwise ops (kPartProd),
 // reduce_scale.hip for the post-scaled sums (kPartScale), reduce_f8.hip
 // for every op of the two OCP FP8 types (kPartF8), reduce_widen.hip for the
-// widened sums (kPartWiden) and reduce_accum.hip for the accumulating widened
-// sums (kPartAccum; the last three are included from reduce_scale.hip).  All
+// widened sums (kPartWiden), reduce_accum.hip for the accumulating widened
+// sums (kPartAccum) and reduce_mixed.hip for the mixed plan kernels
+// (kPartMixed; the last four are included from reduce_scale.hip).  All
 // take their ops from the one list below (with_elem<PART>), so a type or an
 // operator is still added in one place.  Everything here is in an anonymous
 // namespace: a kernel belongs to the unit that instantiates it.
@@ -1525,6 +1526,48 @@ __global__ __launch_bounds__(BLOCK) void k_reduce_plan_scaled(PlanArgsScaled a) 
   });
 }
 
+// The MIXED plan kernel (kOpMixedSum): k_reduce_plan_scaled whose computes are
+// scaled or not one by one -- PlanDesc.pad bit 3 (kDescUnscaled) set: this
+// compute writes the plain sum.  A step of an averaging Comm<T> holds final
+// computes (scaled) next to intermediate ones (plain) and stays one launch.
+// The unit's finishing factor is alpha or ONE: the descriptor word is a scalar
+// load and the choice a scalar select, so no lane diverges and the unit's code
+// is the scaled kernel's.  Multiplying by one gives the plain sum's word for
+// every non-NaN sum (fl(s * 1) = s, subnormals and signed zeros included;
+// round_T(fl32(widen(s) * 1)) = s because widen is exact and s is in T's
+// range; with an f32 accumulator round_T(s32), the WIDE sum), and a NaN stays
+// a NaN.  A third body of its own, like the two above and for their reason.
+template <class Op, int BLOCK, int U, int POL, int ENG>
+__global__ __launch_bounds__(BLOCK) void k_reduce_plan_mixed(PlanArgsScaled a) {
+  const fin_t<Op> fin_alpha = Op::fin(a.scale);
+  const fin_t<Op> fin_one = Op::fin(Scale{1.0, 1.0f, 0u});
+  const int tid = threadIdx.x;
+  uint32_t voff[U];
+#pragma unroll
+  for (int u = 0; u < U; u++) voff[u] = (uint32_t)((u * BLOCK + tid) * kPacket);
+  constexpr uint64_t TILE = (uint64_t)BLOCK * U;
+  for_each_unit(a.sched, a.grab, a.t_begin, a.t_end, [&](uint64_t t, auto hook) {
+    const uint32_t c = a.unit_comp ? ((ConstU32 *)a.unit_comp)[t] : 0u;
+    const PlanDesc d = load_desc(a.desc, c);
+    const uint32_t flags = ((const ConstDesc *)a.desc + c)->pad;  // scalar load, with the descriptor's other words
+    const fin_t<Op> fin = (flags & kDescUnscaled) ? fin_one : fin_alpha;
+    const uint64_t lt = t - d.tile_begin;
+    TableInputs raw{a.ptrs + (uint64_t)c * a.stride};
+    if (lt == 0) scalar_part<Op, POL>(d.out, raw, d.n, d.head, d.npkt, d.tail, tid, fin);
+    const uint64_t pkt0 = lt * TILE;
+    if (pkt0 >= d.npkt) {  // a scalar-only compute: nothing to load or store
+      hook();
+      return;
+    }
+    const uint64_t shift = (uint64_t)d.head * Op::kEsz;
+    Shifted<TableInputs> in{raw, shift};
+    const uint64_t left = d.npkt - pkt0;
+    const uint32_t tile_bytes = (uint32_t)((left < TILE ? left : TILE) * kPacket);
+    unit_body<Op, U, POL, ENG>(d.out + (uint64_t)d.head * out_esz<Op>(), in, d.n, pkt0 * kPacket, tile_bytes, voff, hook,
+                               fin);
+  });
+}
+
 // ------------------------------------------------------------ step programs --
 //
 // A stream-ordered pipeline step is a short ordered list: ready-token phases,
@@ -1736,6 +1779,7 @@ constexpr int kPartScale = 3;  // post-scaled sums (kOpScaledSum)
 constexpr int kPartF8 = 4;  // the OCP FP8 types, every operator they have
 constexpr int kPartWiden = 5;  // widened sums (kOpWidenSum): 2-byte and FP8 inputs, f32 output
 constexpr int kPartAccum = 6;  // accumulating widened sums (kOpWidenAccum): out += alpha * sum
+constexpr int kPartMixed = 7;  // mixed plans (kOpMixedSum): the scaled ops of all six floating types, plan kernels only
 
 // MAX and MIN of the six arithmetic types; HICCL_BYTES has no operator.
 template <bool MAX, class R, class F>
@@ -1868,7 +1912,19 @@ R with_elem_accum(int dtype, int acc, R unknown, F f) {
 
 template <int PART, class R, class F>
 R with_elem(int dtype, int acc, int op, R unknown, F f) {
-  if constexpr (PART == kPartAccum) {
+  if constexpr (PART == kPartMixed) {  // the scaled ops themselves, FP8's included
+    if (op != kOpMixedSum) return unknown;
+    const bool wide = acc == HICCL_ACC_WIDE;
+    switch (dtype) {  // (not through with_elem_f8: f would be instantiated for FP8's unscaled ops too)
+      case HICCL_FLOAT8_E4M3:
+        return wide ? f(Elem<HICCL_FLOAT8_E4M3, OpF8Scaled<OpF8Wide<kE4M3>, kE4M3>, false>())
+                    : f(Elem<HICCL_FLOAT8_E4M3, OpF8Scaled<OpF8<kE4M3>, kE4M3>, false>());
+      case HICCL_FLOAT8_E5M2:
+        return wide ? f(Elem<HICCL_FLOAT8_E5M2, OpF8Scaled<OpF8Wide<kE5M2>, kE5M2>, false>())
+                    : f(Elem<HICCL_FLOAT8_E5M2, OpF8Scaled<OpF8<kE5M2>, kE5M2>, false>());
+      default: return with_elem_scale(dtype, acc, unknown, f);
+    }
+  } else if constexpr (PART == kPartAccum) {
     return op == kOpWidenAccum ? with_elem_accum(dtype, acc, unknown, f) : unknown;
   } else if constexpr (PART == kPartWiden) {
     return op == kOpWidenSum ? with_elem_widen(dtype, acc, unknown, f) : unknown;
@@ -2045,6 +2101,33 @@ plan_fn pick_plan_eng(int engine, int unroll, int pol) {
     case 10 * S + kPolLoadSys: return pick_plan_pol<Op, TUNED, 10 * S + kPolLoadSys>(engine, unroll);
     case 10 * kPolStoreSys + kPolLoadSys:
       return pick_plan_pol<Op, TUNED, 10 * kPolStoreSys + kPolLoadSys>(engine, unroll);
+    default: return nullptr;
+  }
+}
+
+// The mixed plan kernels (k_reduce_plan_mixed): the shapes the scaled plan
+// kernels have -- either engine's default shape under the four plan policies
+// (default, write-through stores, peer loads, both) -- and no tuning table.
+template <class Op, int ENG, int U, int POL>
+void launch_plan_mixed_t(const PlanArgsScaled &a, dim3 grid, hipStream_t s) {
+  constexpr int B = ENG == kPhase ? kPhBlock : kDefBlock;
+  hipLaunchKernelGGL((k_reduce_plan_mixed<Op, B, U, POL, ENG>), grid, dim3(B), 0, s, a);
+}
+
+template <class Op, int POL>
+plan_fn pick_plan_mixed_pol(int engine, int unroll) {
+  if (engine == HICCL_ENGINE_PHASE) return launch_plan_mixed_t<Op, kPhase, phase_p_of<Op>(), POL>;
+  return unroll == 0 || unroll == kDefUnroll ? launch_plan_mixed_t<Op, kTile, kDefUnroll, POL> : nullptr;
+}
+
+template <class Op>
+plan_fn pick_plan_mixed_eng(int engine, int unroll, int pol) {
+  constexpr int L = kDefPol % 10, S = kDefPol / 10;
+  switch (pol) {
+    case kDefPol: return pick_plan_mixed_pol<Op, kDefPol>(engine, unroll);
+    case 10 * kPolStoreSys + L: return pick_plan_mixed_pol<Op, 10 * kPolStoreSys + L>(engine, unroll);
+    case 10 * S + kPolLoadSys: return pick_plan_mixed_pol<Op, 10 * S + kPolLoadSys>(engine, unroll);
+    case 10 * kPolStoreSys + kPolLoadSys: return pick_plan_mixed_pol<Op, 10 * kPolStoreSys + kPolLoadSys>(engine, unroll);
     default: return nullptr;
   }
 }

@@ -58,6 +58,15 @@ constexpr int kOpWidenSum = 0x101;
 // holds; is_widen_op answers for both.
 constexpr int kOpWidenAccum = 0x102;
 constexpr bool is_widen_op(int op) { return op == kOpWidenSum || op == kOpWidenAccum; }
+// A scaled plan in which some computes, not all, write the plain sum
+// (hiccl_reduce_plan_add_unscaled: the intermediate computes of an averaging
+// Comm<T> step): the MIXED plan kernels, which read the choice per compute from
+// PlanDesc.pad (kDescUnscaled).  Plan kernels only; the policy takes it for
+// kOpScaledSum.  No public entry takes it either.
+constexpr int kOpMixedSum = 0x103;
+// PlanDesc.pad bit 3: this compute of a mixed launch is not scaled (bits 0-2
+// are the step programs': byte copy, peer flags)
+constexpr uint32_t kDescUnscaled = 8u;
 
 // The scale of a scaled sum: alpha as the caller gave it (f64 kernels) and
 // rounded to nearest even to f32 (every other type).  The scaled kernels take
@@ -210,6 +219,8 @@ plan_fn pick_plan_widen(int dtype, int acc, int op, int engine, int unroll, int 
 // the accumulating widened sums (reduce_accum.hip; op == kOpWidenAccum, dtype: the inputs'): no program kernels
 single_fn pick_single_accum(int dtype, int acc, int op, int engine, int block, int unroll, int pol);
 plan_fn pick_plan_accum(int dtype, int acc, int op, int engine, int unroll, int pol);
+// the mixed plan kernels (reduce_mixed.hip; op == kOpMixedSum, the six floating dtypes): plan kernels only
+plan_fn pick_plan_mixed(int dtype, int acc, int op, int engine, int unroll, int pol);
 
 // ---- the plain kernels
 

@@ -127,7 +127,9 @@ int plan_upload(hiccl_reduce_plan *p, hipStream_t s) {
   p->unroll = c.unroll;
   p->bpc = c.bpc;
   DescTable t(maxn, unit_pkts(p->engine, p->dtype, c.acc, p->unroll, c.op));
-  for (auto &cp : p->comps) t.add(cp.out, cp.in.data(), cp.in.size(), cp.count, p->osz);
+  // (the flag is read by the mixed kernels alone: every other plan kernel takes pad for zero)
+  for (auto &cp : p->comps)
+    t.add(cp.out, cp.in.data(), cp.in.size(), cp.count, p->osz, cp.unscaled ? kDescUnscaled : 0u);
   const std::vector<char> host = t.image();
   if (int e = check_hip(hipMalloc((void **)&p->d_block, host.size()), "plan: hipMalloc")) return e;
   if (int e = check_hip(hipMemcpy(p->d_block, host.data(), host.size(), hipMemcpyHostToDevice), "plan: upload"))
@@ -355,7 +357,7 @@ int hiccl_reduce_plan_set_config(hiccl_reduce_plan_t *p, const hiccl_reduce_conf
     return fail(hipErrorInvalidValue, "plan_set_config: a widened plan always accumulates in f32: leave acc at "
                                       "HICCL_ACC_NATIVE");
   // the shape must be one the plan kernels have, whatever engine AUTO picks
-  const std::string why = plan_config_error(p, c, p->kernel_op());
+  const std::string why = plan_config_error(p, c, p->config_op());
   if (!why.empty()) return fail(hipErrorInvalidValue, "plan_set_config: " + why);
   p->req = c;
   p->dirty = true;
@@ -364,10 +366,13 @@ int hiccl_reduce_plan_set_config(hiccl_reduce_plan_t *p, const hiccl_reduce_conf
 
 int hiccl_reduce_plan_engine(const hiccl_reduce_plan_t *p) { return p ? p->engine : -1; }
 
-int hiccl_reduce_plan_add(hiccl_reduce_plan_t *p, void *out, const void *const *in, int n,
-                          size_t count) {
-  if (!p) return fail(hipErrorInvalidValue, "plan_add: plan is NULL");
-  if (p->dtype == HICCL_BYTES && n != 1) return fail(hipErrorInvalidValue, "plan_add: HICCL_BYTES copies need n == 1");
+static int plan_add_impl(hiccl_reduce_plan_t *p, void *out, const void *const *in, int n, size_t count, bool unscaled,
+                         const std::string &who) {
+  if (!p) return fail(hipErrorInvalidValue, who + ": plan is NULL");
+  if (unscaled && p->widened)
+    return fail(hipErrorInvalidValue, who + ": a widened or accumulating plan takes no unscaled compute (its kernels "
+                                            "always multiply: one scale per plan)");
+  if (p->dtype == HICCL_BYTES && n != 1) return fail(hipErrorInvalidValue, who + ": HICCL_BYTES copies need n == 1");
   if (p->widened) {
     if (int e = check_buffers_widened(out, in, n, count, p->esz, p->osz)) return e;
   } else if (int e = check_buffers(out, in, n, count, p->esz)) {
@@ -378,10 +383,22 @@ int hiccl_reduce_plan_add(hiccl_reduce_plan_t *p, void *out, const void *const *
   c.out = out;
   c.in.assign(in, in + n);
   c.count = count;
+  c.unscaled = unscaled;
   p->comps.push_back(std::move(c));
-  p->dirty = true;
+  if (unscaled) p->num_unscaled++;
+  p->dirty = true;  // (and the kernel family of a scaled plan may change: kernel_op)
   return 0;
 }
+
+int hiccl_reduce_plan_add(hiccl_reduce_plan_t *p, void *out, const void *const *in, int n, size_t count) {
+  return plan_add_impl(p, out, in, n, count, false, "plan_add");
+}
+
+int hiccl_reduce_plan_add_unscaled(hiccl_reduce_plan_t *p, void *out, const void *const *in, int n, size_t count) {
+  return plan_add_impl(p, out, in, n, count, true, "plan_add_unscaled");
+}
+
+int hiccl_reduce_plan_num_unscaled(const hiccl_reduce_plan_t *p) { return p ? (int)p->num_unscaled : 0; }
 
 int hiccl_reduce_plan_enqueue(hiccl_reduce_plan_t *p, void *stream) {
   if (int e = plan_enqueue_impl(p, (hipStream_t)stream, "plan_enqueue")) return e;
@@ -416,8 +433,10 @@ int hiccl_reduce_plan_launch_each(hiccl_reduce_plan_t *p, void *stream) {
   // compute alone (the reference's structure, compute.h:88-91).
   const Scale sc = p->kernel_scale();
   for (auto &c : p->comps) {
-    if (int e = reduce_call(p->dtype, p->kernel_op(), p->has_scale() ? &sc : nullptr, c.out, c.in.data(),
-                            (int)c.in.size(), c.count, stream, &p->req))
+    // an unscaled compute of a scaled plan is a plain sum (a widened plan has none)
+    const bool plain = !p->widened && (!p->scaled || c.unscaled);
+    if (int e = reduce_call(p->dtype, plain ? p->op : p->widened ? p->kernel_op() : kOpScaledSum, plain ? nullptr : &sc,
+                            c.out, c.in.data(), (int)c.in.size(), c.count, stream, &p->req))
       return e;
   }
   p->launched = true;

@@ -17,10 +17,17 @@ struct hiccl_reduce_plan {
   bool widened = false;           // hiccl_reduce_plan_set_out_dtype: dtype inputs, f32 outputs (op stays SUM)
   // the operator the policy and the kernel tables see
   bool accumulate = false;        // hiccl_reduce_plan_set_accumulate: out += (alpha *) sum, on a widened plan only
+  // A scaled plan's family follows its computes: all scaled -- the scaled
+  // kernels; all unscaled (hiccl_reduce_plan_add_unscaled) -- the plain SUM
+  // kernels, tuned table included; both kinds -- the mixed kernels.
   int kernel_op() const {
-    return widened ? (accumulate ? hiccl_impl::kOpWidenAccum : hiccl_impl::kOpWidenSum)
-                   : scaled ? hiccl_impl::kOpScaledSum : op;
+    if (widened) return accumulate ? hiccl_impl::kOpWidenAccum : hiccl_impl::kOpWidenSum;
+    if (!scaled || num_unscaled == comps.size()) return op;
+    return num_unscaled ? hiccl_impl::kOpMixedSum : hiccl_impl::kOpScaledSum;
   }
+  // the operator a config is validated for: the scaled kernels' shapes are the
+  // mixed ones' and a subset of the plain sums', whatever computes come later
+  int config_op() const { return !widened && scaled ? hiccl_impl::kOpScaledSum : kernel_op(); }
   // the scale a launch carries: a widened plan's kernels always multiply (by one if unscaled)
   hiccl_impl::Scale kernel_scale() const { return widened && !scaled ? hiccl_impl::Scale{1.0, 1.0f, 0u} : scale; }
   bool has_scale() const { return scaled || widened; }
@@ -37,8 +44,10 @@ struct hiccl_reduce_plan {
     void *out;
     std::vector<const void *> in;
     size_t count;
+    bool unscaled = false;  // hiccl_reduce_plan_add_unscaled: the plain sum, whatever the plan's scale
   };
   std::vector<Comp> comps;
+  size_t num_unscaled = 0;  // computes with the flag
   bool dirty = true;
   char *d_block = nullptr;  // the uploaded DescTable
   hiccl_impl::PlanArgs args;  // pointers into d_block
@@ -66,7 +75,8 @@ struct DescTable {
   uint64_t units = 0;
 
   DescTable(size_t stride_, uint64_t unit_) : stride(stride_ ? stride_ : 1), unit(unit_) {}
-  // One compute; `flags` goes to PlanDesc.pad (k_program: byte copy, peer policy).
+  // One compute; `flags` goes to PlanDesc.pad (k_program: byte copy, peer
+  // policy; k_reduce_plan_mixed: kDescUnscaled).
   void add(void *out, const void *const *in, size_t n, size_t count, size_t esz, uint32_t flags = 0);
 
   size_t ptrs_off() const { return desc.size() * sizeof(PlanDesc); }

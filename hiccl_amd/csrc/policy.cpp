@@ -20,6 +20,10 @@
 // either accumulator: it takes the rules of an untuned operator of its dtype,
 // and none has been measured for it beyond M20's one f32 shape.
 //
+// A mixed plan (kOpMixedSum: a scaled plan some of whose computes are
+// unscaled) takes the scaled sum's rules word for word (threshold_op); its
+// kernels have the scaled plan kernels' shapes.  One measurement: M24.
+//
 // The OCP FP8 types (HICCL_FLOAT8_E4M3, HICCL_FLOAT8_E5M2) are untuned under
 // every operator and either accumulator: they take the rules f64 takes (no
 // wide or half-size tile, no rule of the tuned types), with their own chunk
@@ -90,7 +94,9 @@ constexpr uint64_t kPacedGridNum = 7, kPacedGridDen = 8;
 // threshold, so both sums resolve to the same engine, grid and store form, and
 // only the shape its PHASE kernels run differs (phase_p with the launch's own
 // operator: finish_cfg, unit_pkts, plan_shape_error).
-inline int threshold_op(int op) { return op == kOpWidenAccum ? kOpWidenSum : op; }
+// A mixed plan (kOpMixedSum: scaled per compute) takes the scaled sum's: its
+// kernels are the scaled ones with a factor chosen per unit.
+inline int threshold_op(int op) { return op == kOpWidenAccum ? kOpWidenSum : op == kOpMixedSum ? kOpScaledSum : op; }
 
 constexpr int kDefBpc = 1;
 constexpr int kSmallBpc = 4;

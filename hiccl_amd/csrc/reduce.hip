@@ -190,6 +190,7 @@ single_fn pick_single(int dtype, int acc, int op, int engine, int block, int unr
 }
 
 plan_fn pick_plan(int dtype, int acc, int op, int engine, int unroll, int pol) {
+  if (op == kOpMixedSum) return pick_plan_mixed(dtype, acc, op, engine, unroll, pol);  // (reduce_mixed.hip)
   if (op == kOpWidenAccum) return pick_plan_accum(dtype, acc, op, engine, unroll, pol);
   if (op == kOpWidenSum) return pick_plan_widen(dtype, acc, op, engine, unroll, pol);
   if (is_f8(dtype)) return pick_plan_f8(dtype, acc, op, engine, unroll, pol);

@@ -9,7 +9,8 @@
 // unit too, behind the scaled sums': the library stays at four code objects
 // with this one last, which the ISA tier of the scaled sums relies on.  The
 // widened sums' kernels (reduce_widen.hip) follow them, for the same reason,
-// and the accumulating widened sums' (reduce_accum.hip) follow those.
+// and the accumulating widened sums' (reduce_accum.hip) follow those, and the
+// mixed plan kernels (reduce_mixed.hip) come last.
 #include "engine.h"
 
 namespace hiccl_impl {
@@ -27,3 +28,4 @@ plan_fn pick_plan_scale(int dtype, int acc, int op, int engine, int unroll, int 
 #include "reduce_f8.hip"
 #include "reduce_widen.hip"
 #include "reduce_accum.hip"
+#include "reduce_mixed.hip"

@@ -43,8 +43,27 @@ struct Schedule {
     bcast_epoch.emplace_back();
     reduce_epoch.emplace_back();
   }
-  void reduce(T *sb, size_t so, T *rb, size_t ro, size_t count, std::vector<int> ids, int recvid) {
-    reduce_epoch.back().emplace_back(sb, so, rb, ro, count, std::move(ids), recvid);
+  // `scaled`: the receiver ends up with finish(sum, alpha) (Comm<T>::set_scale)
+  void reduce(T *sb, size_t so, T *rb, size_t ro, size_t count, std::vector<int> ids, int recvid, bool scaled = false,
+              double alpha = 1.0) {
+    const int prim = (int)prims.size();
+    prims.push_back({count, ids.size(), recvid, scaled, alpha});
+    reduce_epoch.back().emplace_back(sb, so, rb, ro, count, std::move(ids), recvid, scaled, prim);
+  }
+  std::vector<typename Planner<T>::Prim> prims;  // one per REDUCE, in the order added
+
+  // The one alpha of the scaled primitives (nullptr: none is scaled).  A
+  // step's kernel arguments hold one alpha, so a second one is refused.
+  const double *scale() const {
+    const double *a = nullptr;
+    for (auto &p : prims) {
+      if (!p.scaled) continue;
+      if (a && *a != p.alpha)
+        CommBench::die("Comm::init", "scaled primitives carry different alphas (" + std::to_string(*a) + " and " +
+                                         std::to_string(p.alpha) + "): one alpha per communicator");
+      if (!a) a = &p.alpha;
+    }
+    return a;
   }
   void bcast(T *sb, size_t so, T *rb, size_t ro, size_t count, int sendid, std::vector<int> ids) {
     bcast_epoch.back().emplace_back(sb, so, rb, ro, count, sendid, std::move(ids));
@@ -91,6 +110,7 @@ struct Schedule {
         }
       }
     }
+    P.check_finals(batches, prims);
     return batches;
   }
 };
@@ -161,10 +181,33 @@ class Comm {
     for (size_t i = 0; i < sch.hierarchy.size(); i++)
       std::printf("  level %zu factor: %d library: %s\n", i, sch.hierarchy[i], CommBench::lib_name(sch.library[i]));
     std::printf("numstripe: %d\nringnodes: %d\npipedepth: %d\n", sch.numstripe, sch.ringnodes, sch.pipedepth);
+    if (const double *a = sch.scale()) std::printf("scale: %.17g (averaging reductions: set_scale)\n", *a);
     std::printf("sendbuf: %p, sendcount %zu\nrecvbuf: %p, recvcount %zu\n", (void *)sendbuf, sendcount,
                 (void *)recvbuf, recvcount);
     std::printf("*********************************\n");
   }
+
+  // Averaging reductions: every REDUCE primitive added while a scale is set
+  // (add_reduce / add_reduction in every spelling) leaves finish(s, alpha) in
+  // its receiver's `count` elements -- s the word the same communicator
+  // produces without the scale (same schedule, same order of every add), finish
+  // the finishing step of a scaled sum (Compute<T>::set_scale), applied ONCE per
+  // element, in the compute that completes the sum (Coll::Comp::final); the
+  // other computes of a step stay plain in the same launch.  Multicasts never
+  // scale.  Floating T only; alpha finite (as a float too, unless T is double);
+  // one alpha per communicator (init() refuses a second one), and a scaled
+  // primitive whose schedule has no compute (one sender) is refused by init().
+  void set_scale(double a) {
+    static_assert(op_of<T>() == 0, "HiCCL::Comm::set_scale: only sums are scaled (T is an operator wrapper)");
+    static_assert(scalable_dtype(dtype_of<T>()),
+                  "HiCCL::Comm::set_scale: floating element types only (float, double, bf16, f16, _Float16, f8e4m3, "
+                  "f8e5m2)");
+    if (!std::isfinite(a) || (!std::is_same<T, double>::value && !std::isfinite((float)a)))
+      CommBench::die("Comm::set_scale", "alpha must be finite");
+    scaling = true;
+    alpha = a;
+  }
+  void clear_scale() { scaling = false; }
 
   // ------------------------------------------------------- primitives ----
   void add_fence() {
@@ -185,10 +228,10 @@ class Comm {
 
   // comm.h:144-156 (add_reduce) -- sendids as a list, a rank, or a pattern
   void add_reduce(T *sb, size_t so, T *rb, size_t ro, size_t count, std::vector<int> &sendids, int recvid) {
-    sch.reduce(sb, so, rb, ro, count, sendids, recvid);
+    sch.reduce(sb, so, rb, ro, count, sendids, recvid, scaling, alpha);
   }
   void add_reduce(T *sb, size_t so, T *rb, size_t ro, size_t count, int sendid, int recvid) {
-    sch.reduce(sb, so, rb, ro, count, expand_ids(sendid, CommBench::numproc, recvid), recvid);
+    sch.reduce(sb, so, rb, ro, count, expand_ids(sendid, CommBench::numproc, recvid), recvid, scaling, alpha);
   }
   void add_reduce(T *sb, size_t so, T *rb, size_t ro, size_t count, pattern p, int recvid) {
     add_reduce(sb, so, rb, ro, count, p == others ? -1 : CommBench::numproc, recvid);
@@ -226,7 +269,8 @@ class Comm {
       owned.push_back(p);
       return p;
     });
-    coll_batch = sch.factorize(P);
+    const double *scale = sch.scale();  // (dies on a second alpha)
+    coll_batch = sch.factorize(P);  // (dies on a scaled primitive without a compute)
     libs = libraries_used(coll_batch);
     steps = merge_steps(coll_batch, libs, 1);
 #ifndef HICCL_PORT_HOST
@@ -253,10 +297,16 @@ class Comm {
       if (CommBench::myid == CommBench::printid) std::printf("HiCCL: graph replay off (XCCL level on RCCL)\n");
     }
     CommBench::stream_ordered = streamed;
-    command_batch = instantiate(steps, libs, fused);
+    command_batch = instantiate(steps, libs, fused, scale);
     CommBench::stream_ordered = false;
 #ifndef HICCL_PORT_HOST
     programs = streamed && want_programs();
+    if (programs && scale) {  // hiccl_program_add_plan takes no plan that has a scale
+      programs = false;
+      if (CommBench::myid == CommBench::printid)
+        std::printf("HiCCL: scaled reductions run one launch per element (step programs take no scaled plan: "
+                    "HICCL_STEP_PROGRAM is not used)\n");
+    }
     if (streamed) {  // one flag pair per registered transfer, every rank the same layout
       size_t total = 0;
       for (auto &lst : command_batch)
@@ -437,6 +487,8 @@ class Comm {
 
  private:
   Schedule<T> sch;
+  bool scaling = false;  // set_scale / clear_scale: what the next add_reduce carries
+  double alpha = 1.0;
   int numepoch = 0;
   T *sendbuf = nullptr, *recvbuf = nullptr;
   size_t sendcount = 0, recvcount = 0;

@@ -89,14 +89,22 @@ struct Command {
 // `fuse`: transfers whose receive buffer only feeds a compute of the same
 // step (Coll::Xfer::feeds) are not copied; the compute reads the sender's
 // buffer in place through its IPC mapping (fused gather + reduce).
+// `scale`: the communicator's alpha (Comm<T>::set_scale) or nullptr.  Every
+// step's Compute then carries the scale and each compute is added unscaled
+// unless it is final (Coll::Comp::final): one launch per step, the multiply
+// once per element.  Without it the calls are those of an unscaled Comm<T>.
 template <typename T>
 std::vector<std::list<Command<T>>> instantiate(const std::vector<std::vector<Coll<T>>> &steps,
-                                               const std::vector<CommBench::library> &libs, bool fuse = false) {
+                                               const std::vector<CommBench::library> &libs, bool fuse = false,
+                                               const double *scale = nullptr) {
   std::vector<std::list<Command<T>>> pipeline(libs.size());
   for (auto &step : steps) {
     for (size_t i = 0; i < libs.size(); i++) {
       auto *comm = new CommBench::Comm<T>(libs[i]);
       auto *comp = new Compute<T>();
+      if constexpr (op_of<T>() == 0 && scalable_dtype(dtype_of<T>())) {
+        if (scale) comp->set_scale(*scale);  // before the first add
+      }
       for (auto &x : step[i].xfers)
         comm->add(x.sendbuf, x.sendoffset, x.recvbuf, x.recvoffset, x.count, x.sendid, x.recvid, fuse && x.feeds);
       for (auto &c : step[i].comps) {
@@ -108,7 +116,10 @@ std::vector<std::list<Command<T>>> instantiate(const std::vector<std::vector<Col
               p = remote;
               peer = true;
             }
-        comp->add(in, c.output, c.count, c.compid, peer);
+        if (scale)
+          comp->add(in, c.output, c.count, c.compid, peer, !c.final);
+        else
+          comp->add(in, c.output, c.count, c.compid, peer);
       }
       pipeline[i].emplace_back(comm, comp);
     }

@@ -93,11 +93,15 @@ class Compute {
   // `peer_inputs`: some input is a peer GPU's buffer read in place (fused
   // gather): the step's kernel then loads with system scope
   // (hiccl_reduce_plan_set_peer).
-  void add(std::vector<T *> &in, T *out, size_t n, int compid, bool peer_inputs = false) {
+  // `unscaled`: this compute writes the plain sum whatever the scale
+  // (hiccl_reduce_plan_add_unscaled) -- an intermediate compute of an
+  // averaging Comm<T> step, next to the final ones in the same launch.
+  void add(std::vector<T *> &in, T *out, size_t n, int compid, bool peer_inputs = false, bool unscaled = false) {
     if (CommBench::myid != compid) return;
     inputbuf.push_back(in);
     outputbuf.push_back(out);
     count.push_back(n);
+    plain.push_back(unscaled ? 1 : 0);
     numcomp++;
 #ifndef HICCL_PORT_HOST
     static_assert(dtype_of<T>() >= 0, "HiCCL::Compute: unsupported element type");
@@ -117,7 +121,10 @@ class Compute {
     }
     if (peer_inputs && !(hiccl_reduce_plan_peer(plan) & HICCL_PEER_LOADS))
       check(hiccl_reduce_plan_set_peer(plan, hiccl_reduce_plan_peer(plan) | HICCL_PEER_LOADS), "plan_set_peer");
-    check(hiccl_reduce_plan_add(plan, out, (const void *const *)in.data(), (int)in.size(), n), "plan_add");
+    if (unscaled)
+      check(hiccl_reduce_plan_add_unscaled(plan, out, (const void *const *)in.data(), (int)in.size(), n), "plan_add_unscaled");
+    else
+      check(hiccl_reduce_plan_add(plan, out, (const void *const *)in.data(), (int)in.size(), n), "plan_add");
 #else
     (void)peer_inputs;
 #endif
@@ -127,8 +134,8 @@ class Compute {
   // start() on (an average: alpha = 1 / inputs) -- in the sum's own pass, the
   // multiply once per element at store time (hiccl_reduce_plan_set_scale; the
   // host port applies the same scale_finish after host_sum, same bits).
-  // Floating T only; alpha must be finite.  A Comm<T> schedule cannot use it
-  // yet: this is for a single-level reduction.
+  // Floating T only; alpha must be finite.  A compute added `unscaled` keeps
+  // writing the plain sum: Comm<T>::set_scale builds its steps from both kinds.
   void set_scale(double alpha) {
     static_assert(op_of<T>() == 0, "HiCCL::Compute::set_scale: only sums are scaled (T is an operator wrapper)");
     static_assert(scalable_dtype(dtype_of<T>()),
@@ -155,7 +162,7 @@ class Compute {
 #ifndef HICCL_PORT_HOST
     check(hiccl_reduce_plan_launch(plan, compute_stream()), "plan_launch");
 #else
-    for (int c = 0; c < numcomp; c++) host_sum(outputbuf[c], count[c], inputbuf[c], scaled, scale);
+    for (int c = 0; c < numcomp; c++) host_sum(outputbuf[c], count[c], inputbuf[c], scaled && !plain[c], scale);
 #endif
   }
 
@@ -274,6 +281,7 @@ class Compute {
  private:
   bool scaled = false;  // set_scale / clear_scale
   double scale = 1.0;
+  std::vector<char> plain;  // per compute: added unscaled
 #ifndef HICCL_PORT_HOST
   hiccl_reduce_plan_t *plan = nullptr;
   static void check(int e, const char *what) {

@@ -65,8 +65,19 @@ struct REDUCE {
   size_t count;
   std::vector<int> sendids;
   int recvid;
-  REDUCE(T *sb, size_t so, T *rb, size_t ro, size_t c, std::vector<int> ids, int rid)
-      : sendbuf(sb), sendoffset(so), recvbuf(rb), recvoffset(ro), count(c), sendids(std::move(ids)), recvid(rid) {}
+  // Comm<T>::set_scale: the receiver ends up with finish(sum, alpha).  The
+  // compute that completes the sum over all of `sendids` is this reduce's FINAL
+  // compute and alone multiplies; a reduce derived from this one (stripe,
+  // reduce_ring, reduce_tree) keeps the flag only where ITS complete sum is the
+  // primitive's.  `prim` names the user's primitive and `origin` this piece's
+  // first element in it (partition, stripe), for the planner's own check.
+  bool scaled = false;
+  int prim = -1;
+  size_t origin = 0;
+  REDUCE(T *sb, size_t so, T *rb, size_t ro, size_t c, std::vector<int> ids, int rid, bool sc = false, int pr = -1,
+         size_t org = 0)
+      : sendbuf(sb), sendoffset(so), recvbuf(rb), recvoffset(ro), count(c), sendids(std::move(ids)), recvid(rid),
+        scaled(sc), prim(pr), origin(org) {}
 };
 
 // Multicast primitive (broadcast.h:2-67).
@@ -100,6 +111,12 @@ struct Coll {
     T *output;
     size_t count;
     int compid;
+    // the final compute of a scaled REDUCE (its output holds the complete sum
+    // over all of the primitive's senders): the one that multiplies by alpha.
+    // prim / origin: the primitive and the first of its elements covered here.
+    bool final = false;
+    int prim = -1;
+    size_t origin = 0;
   };
   CommBench::library lib;
   std::vector<Xfer> xfers;
@@ -110,6 +127,10 @@ struct Coll {
     xfers.push_back({sb, so, rb, ro, c, sid, rid, feeds});
   }
   void add(std::vector<T *> in, T *out, size_t c, int compid) { comps.push_back({std::move(in), out, c, compid}); }
+  // a compute of the scaled reduce `r`, final or intermediate
+  void add(std::vector<T *> in, T *out, size_t c, int compid, const REDUCE<T> &r, bool final) {
+    comps.push_back({std::move(in), out, c, compid, r.scaled && final, r.prim, r.origin});
+  }
   int numcomm() const { return (int)xfers.size(); }
   int numcompute() const { return (int)comps.size(); }
   bool empty() const { return xfers.empty() && comps.empty(); }
@@ -129,7 +150,12 @@ struct Coll {
         fanin[c.compid] += (int)c.inputs.size();
         outs[c.compid]++;
       }
-      std::printf(", %d computes:", numcompute());
+      int finals = 0;
+      for (auto &c : comps) finals += c.final ? 1 : 0;
+      if (finals)
+        std::printf(", %d computes (%d final):", numcompute(), finals);
+      else
+        std::printf(", %d computes:", numcompute());
       for (int p = 0; p < np && np < 64; p++)
         if (outs[p]) std::printf(" %d:%d->%d", p, fanin[p], outs[p]);
     }
@@ -171,6 +197,15 @@ class Planner {
       std::vector<int> heads;
       T *mine = nullptr;
       size_t mine_off = 0;
+      // the sum is complete after this level when one group alone holds
+      // senders: its compute is the final one.  (head == r.recvid does not say
+      // so: the receiver writes in place at every level.)
+      int groups = 0;
+      for (int g = 0; g < np / gs; g++) {
+        bool any = false;
+        for (int s : r.sendids) any = any || s / gs == g;
+        groups += any ? 1 : 0;
+      }
       for (int g = 0; g < np / gs; g++) {
         std::vector<int> members;
         for (int s : r.sendids)
@@ -200,7 +235,7 @@ class Planner {
               inputs.push_back(rb);
             }
           }
-          coll->add(std::move(inputs), at(obuf, ooff), r.count, head);
+          coll->add(std::move(inputs), at(obuf, ooff), r.count, head, r, groups == 1);
         } else if (members[0] != head || level == numlevel - 1) {
           output();
           coll->add(r.sendbuf, r.sendoffset, obuf, ooff, r.count, members[0], head);
@@ -214,7 +249,8 @@ class Planner {
           mine_off = ooff;
         }
       }
-      if (!heads.empty()) up.emplace_back(mine, mine_off, r.recvbuf, r.recvoffset, r.count, heads, r.recvid);
+      if (!heads.empty())
+        up.emplace_back(mine, mine_off, r.recvbuf, r.recvoffset, r.count, heads, r.recvid, r.scaled, r.prim, r.origin);
     }
     keep(coll, out);
     reduce_tree(numlevel, gsz, lib, std::move(up), level - 1, out, pool);
@@ -256,7 +292,11 @@ class Planner {
       std::vector<int> rest;
       for (int node = 0; node < numnode; node++)
         if (node != rnode) rest.insert(rest.end(), by_node[node].begin(), by_node[node].end());
-      further.emplace_back(r.sendbuf, r.sendoffset, part, part_off, r.count, rest, fwd);
+      // the ring partial is the complete sum only when the receiver's node adds
+      // nothing: then the final compute is the forwarding rank's, the last of
+      // `further`, and the transfer below moves the finished (scaled) sum
+      further.emplace_back(r.sendbuf, r.sendoffset, part, part_off, r.count, rest, fwd, r.scaled && local.empty(), r.prim,
+                           r.origin);
       T *land;
       size_t land_off = 0;
       if (local.empty()) {
@@ -267,7 +307,8 @@ class Planner {
         land = take(r.recvid, r.count);
         T *mine = take(r.recvid, r.count);
         intra.emplace_back(r.sendbuf, r.sendoffset, mine, 0, r.count, local, r.recvid);
-        coll->add(std::vector<T *>{land, mine}, at(r.recvbuf, r.recvoffset), r.count, r.recvid);
+        // (`intra` into `mine` is a partial too: not scaled; the merge is final)
+        coll->add(std::vector<T *>{land, mine}, at(r.recvbuf, r.recvoffset), r.count, r.recvid, r, true);
       }
       // when `part` is the forwarding rank's own send buffer, `further`
       // holds an empty reduce and this transfer moves the raw data
@@ -315,7 +356,9 @@ class Planner {
           ro = r.recvoffset + off;
           if (me == recver) reuse += cnt;
         }
-        result.emplace_back(r.sendbuf, r.sendoffset + off, rb, ro, cnt, r.sendids, recver);
+        // a stripe's reduce finishes its elements: the merge multicast moves scaled sums
+        result.emplace_back(r.sendbuf, r.sendoffset + off, rb, ro, cnt, r.sendids, recver, r.scaled, r.prim,
+                            r.origin + off);
         off += cnt;
       }
     }
@@ -447,6 +490,54 @@ class Planner {
     return split;
   }
 
+  // ------------------------------------------------- scaled primitives --
+
+  // What the user asked of primitive `prim` (Schedule::reduce).
+  struct Prim {
+    size_t count;
+    size_t nsend;
+    int recvid;
+    bool scaled;
+    double alpha;
+  };
+
+  // The planner's check of its own result: the final computes of every scaled
+  // primitive write each of its `count` elements exactly once.  It counts the
+  // outputs marked final (their origins and lengths must tile [0, count)) and
+  // knows nothing of how the flag travelled.  Every rank holds every entry, so
+  // every rank reaches the same verdict.
+  void check_finals(const std::vector<CollList<T>> &batches, const std::vector<Prim> &prims) const {
+    std::vector<std::vector<std::pair<size_t, size_t>>> pieces(prims.size());
+    std::vector<size_t> computes(prims.size(), 0);
+    for (auto &b : batches)
+      for (auto *coll : b)
+        for (auto &c : coll->comps) {
+          if (c.prim < 0 || (size_t)c.prim >= prims.size()) continue;
+          computes[c.prim]++;
+          if (c.final) pieces[c.prim].emplace_back(c.origin, c.count);
+        }
+    for (size_t p = 0; p < prims.size(); p++) {
+      if (!prims[p].scaled || !prims[p].count) continue;
+      const std::string name = "scaled REDUCE #" + std::to_string(p) + " (" + std::to_string(prims[p].count) +
+                               " elements, " + std::to_string(prims[p].nsend) + " sender(s), receiver " +
+                               std::to_string(prims[p].recvid) + ")";
+      if (!computes[p])
+        CommBench::die("Comm::init", name + ": its factorization holds no compute to scale in (a single sender, such as a "
+                                            "scatter, only moves data); add it without a scale and scale the result");
+      std::sort(pieces[p].begin(), pieces[p].end());
+      size_t next = 0;
+      for (auto &pc : pieces[p]) {
+        if (pc.first != next)
+          CommBench::die("Comm::init", name + ": its final computes " + (pc.first < next ? "write element " : "miss element ") +
+                                           std::to_string(std::min(pc.first, next)) + (pc.first < next ? " twice" : "") +
+                                           " (planner error)");
+        next = pc.first + pc.second;
+      }
+      if (next != prims[p].count)
+        CommBench::die("Comm::init", name + ": its final computes cover " + std::to_string(next) + " elements (planner error)");
+    }
+  }
+
  private:
   Alloc alloc_;
 
@@ -482,6 +573,13 @@ class Planner {
 // reduce.h:401-415 / broadcast.h:321-335: split every primitive into
 // `numbatch` consecutive pieces (count/numbatch, the first count%numbatch
 // pieces one element longer), stopping at the first empty piece.
+template <typename T>
+inline void advance_origin(REDUCE<T> &r, size_t off) {
+  r.origin += off;
+}
+template <typename P>
+inline void advance_origin(P &, size_t) {}
+
 template <typename P>
 std::vector<std::vector<P>> partition(const std::vector<P> &list, int numbatch) {
   std::vector<std::vector<P>> out(numbatch);
@@ -494,6 +592,7 @@ std::vector<std::vector<P>> partition(const std::vector<P> &list, int numbatch) 
       q.sendoffset += off;
       q.recvoffset += off;
       q.count = cnt;
+      advance_origin(q, off);
       out[b].push_back(q);
       off += cnt;
     }

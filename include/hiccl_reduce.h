@@ -437,7 +437,8 @@ int hiccl_reduce_plan_set_op(hiccl_reduce_plan_t *plan, int op);
 int hiccl_reduce_plan_op(const hiccl_reduce_plan_t *plan);
 /* The plan's scale (hiccl_reduce_scaled): every compute of the plan writes
  * finish(sum, *alpha) from the next launch on, launch_each included; NULL
- * turns it off.  May be called at any time, like set_acc (switching it on or
+ * turns it off (a compute added with hiccl_reduce_plan_add_unscaled, below,
+ * keeps writing the plain sum).  May be called at any time, like set_acc (switching it on or
  * off re-uploads at the next launch; a new alpha alone does not: it travels in
  * the kernel arguments, and an enqueue still only reads the plan).  Refused
  * for an integer or HICCL_BYTES plan, a non-finite alpha, a plan whose
@@ -532,6 +533,27 @@ int hiccl_reduce_plan_store_policy(const hiccl_reduce_plan_t *plan);
 int hiccl_reduce_plan_engine(const hiccl_reduce_plan_t *plan);
 int hiccl_reduce_plan_add(hiccl_reduce_plan_t *plan, void *out, const void *const *in, int n,
                           size_t count);
+/* hiccl_reduce_plan_add with one difference: in a plan that has a scale this
+ * compute writes the PLAIN sum of the plan's dtype and accumulator -- the
+ * words a plan without the scale writes, a NaN by NaN-ness.  A hierarchical
+ * schedule reduces in several levels and scales once: a step's launch holds
+ * final computes (add) next to intermediate ones (add_unscaled), and
+ * HiCCL::Comm<T>::set_scale builds its steps so.  On a plan without a scale
+ * it is hiccl_reduce_plan_add; the flag stays with the compute when the scale
+ * is later set, changed or cleared.  Refused, with hipErrorInvalidValue and
+ * before any device work, on a widened or accumulating plan (their kernels
+ * always multiply: one scale per plan).
+ * The kernels of a scaled plan follow its computes, chosen at launch: none
+ * unscaled -- the scaled kernels; every one unscaled -- the plain SUM kernels
+ * of the dtype (with the tuned shapes of f32 / bf16 / f16); both kinds -- the
+ * MIXED plan kernels, one launch, the finishing factor alpha or one per
+ * compute (either engine's default shape, the store and the peer-load forms;
+ * no tuned shape).  launch_each scales compute by compute likewise.
+ * hiccl_program_add_plan keeps refusing any plan that has a scale.
+ * hiccl_reduce_plan_num_unscaled: the computes added with the flag (0 for NULL). */
+int hiccl_reduce_plan_add_unscaled(hiccl_reduce_plan_t *plan, void *out, const void *const *in, int n,
+                                   size_t count);
+int hiccl_reduce_plan_num_unscaled(const hiccl_reduce_plan_t *plan);
 int hiccl_reduce_plan_launch(hiccl_reduce_plan_t *plan, void *stream);
 /* launch without remembering the stream for hiccl_reduce_plan_sync: for
  * stream-ordered callers that synchronise the stream themselves, and for
