@@ -19,7 +19,8 @@ $(PROBE): tools/hbm_probe.hip
 # kernels, reduce_prod.hip, the PROD and bitwise kernels, and reduce_scale.hip,
 # the scaled sums, which also takes in reduce_f8.hip, the OCP FP8 types, and
 # reduce_widen.hip, the widened sums, reduce_accum.hip, the accumulating
-# ones, and reduce_mixed.hip, the mixed plan kernels (the library keeps four code objects, the
+# ones, reduce_mixed.hip, the mixed plan kernels, and reduce_weighted.hip, the
+# weighted widened sums (the library keeps four code objects, the
 # scaled sums' last), compiled side by
 # side (reduce.hip the longest) -- and the host files (seconds each), as
 # objects under build/obj, linked once.  The link order is the order of the
@@ -84,7 +85,8 @@ CPP_BINS = build/plan_dump build/collectives_host build/collectives_host_f32 bui
            build/types_comm_host build/types_comm_hip \
            build/widen_sum build/widen_sum_hip \
            build/accum_sum build/accum_sum_hip \
-           build/avg_comm_host build/avg_comm_hip
+           build/avg_comm_host build/avg_comm_hip \
+           build/weighted_sum build/weighted_sum_hip
 
 cpp: $(CPP_BINS)
 
@@ -261,6 +263,17 @@ build/avg_comm_host: tests/cpp/avg_comm.cpp $(HDRS)
 	$(CXX) $(CXXFLAGS) -fopenmp -DHICCL_PORT_HOST -o $@ $< $(MPI_LINK)
 
 build/avg_comm_hip: tests/cpp/avg_comm.cpp $(HDRS) $(LIB)
+	@mkdir -p build
+	$(CXX) $(CXXFLAGS) $(HIP_HOST) -o $@ $< $(HIP_LINK) $(MPI_LINK)
+
+# Weighted widened sums: WidenCompute<T>::add with per-input weights on the
+# host port -- a stand-alone program that tests/test_weighted_cpu.py also builds
+# with sanitizers -- and on the GPU (tests/test_weighted_gpu.py)
+build/weighted_sum: tests/cpp/weighted_sum.cpp $(HDRS)
+	@mkdir -p build
+	$(CXX) $(CXXFLAGS) -fopenmp -DHICCL_PORT_HOST -o $@ $< $(MPI_LINK)
+
+build/weighted_sum_hip: tests/cpp/weighted_sum.cpp $(HDRS) $(LIB)
 	@mkdir -p build
 	$(CXX) $(CXXFLAGS) $(HIP_HOST) -o $@ $< $(HIP_LINK) $(MPI_LINK)
 

@@ -115,6 +115,15 @@ _SIGS = {
                                                ctypes.c_int, ctypes.c_size_t, _vp, ctypes.POINTER(ReduceConfig)]),
     "hiccl_reduce_auto_choice_accumulate": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ReduceConfig), ctypes.c_size_t,
                                                            ctypes.c_double, ctypes.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "hiccl_reduce_weighted": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.c_int,
+                                             _vp, _vp, _vp, ctypes.c_int, ctypes.c_size_t, _vp,
+                                             ctypes.POINTER(ReduceConfig)]),
+    "hiccl_reduce_auto_choice_weighted": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ReduceConfig),
+                                                         ctypes.c_size_t, ctypes.c_double, ctypes.c_int, _vp, _vp, _vp,
+                                                         _vp, _vp]),
+    "hiccl_reduce_plan_set_weighted": (ctypes.c_int, [_vp, ctypes.c_int]),
+    "hiccl_reduce_plan_weighted": (ctypes.c_int, [_vp]),
+    "hiccl_reduce_plan_add_weighted": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int, ctypes.c_size_t]),
     "hiccl_reduce_plan_set_accumulate": (ctypes.c_int, [_vp, ctypes.c_int]),
     "hiccl_reduce_plan_accumulate": (ctypes.c_int, [_vp]),
     "hiccl_reduce_plan_set_out_dtype": (ctypes.c_int, [_vp, ctypes.c_int]),

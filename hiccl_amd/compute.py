@@ -197,7 +197,32 @@ def _check_accumulate(accumulate, widened=True):
                          "(a same-type sum accumulates by passing out as input 0)")
 
 
-def reduce_widened(out, inputs, count=None, stream=None, config=None, scale=None, accumulate=False):
+def _check_weights(weights, n, out, out_ptr=None, count=None):
+    """The weights of a weighted sum: a contiguous float32 tensor of ``n``
+    elements on the output's device that does not overlap the output -- refused
+    here, before any device work.  A Python sequence is not taken: the caller
+    makes the tensor, so nothing is uploaded behind their back.  Returns the
+    tensor's address."""
+    if not isinstance(weights, torch.Tensor):
+        raise TypeError(f"hiccl: weights must be a torch.float32 tensor on the device, not {type(weights).__name__} "
+                        "(the kernels read the weights from device memory when they run)")
+    if weights.dtype != torch.float32:
+        raise TypeError(f"hiccl: weights must be torch.float32, not {weights.dtype}")
+    if not weights.is_cuda:
+        raise ValueError("hiccl: weights must live in device memory (the kernels read them when they run)")
+    if out is not None and weights.device != out.device:
+        raise ValueError(f"hiccl: weights are on {weights.device}, out on {out.device}")
+    if not weights.is_contiguous():
+        raise ValueError("hiccl: weights must be contiguous")
+    if weights.numel() != n:
+        raise ValueError(f"hiccl: {weights.numel()} weights for {n} inputs")
+    w0 = weights.data_ptr()
+    if out_ptr is not None and count and n and w0 < out_ptr + 4 * count and out_ptr < w0 + 4 * n:
+        raise ValueError("hiccl: the weights overlap the output")
+    return w0
+
+
+def reduce_widened(out, inputs, count=None, stream=None, config=None, scale=None, accumulate=False, weights=None):
     """out[:count] = ((0.0f + float(inputs[0])) + float(inputs[1])) + ... in the
     list order, every add an f32 add: bf16, f16 or FP8 ``inputs`` (one dtype)
     summed into a ``torch.float32`` ``out`` in one pass (hiccl_reduce_widened)
@@ -214,6 +239,15 @@ def reduce_widened(out, inputs, count=None, stream=None, config=None, scale=None
     ``accumulate=True``: ``out += scale * sum`` (hiccl_reduce_accumulate) --
     the sum is finished first, scaled, then added to ``out`` as it was: three
     separately rounded f32 operations.  Every call adds once more.
+
+    ``weights``: a contiguous ``torch.float32`` tensor of ``len(inputs)``
+    elements on ``out``'s device; input k then counts as
+    ``fl32(weights[k] * float(inputs[k]))`` (hiccl_reduce_weighted: a multiply
+    and an add, separately rounded -- the words of ``reduce`` on the f32 copies
+    ``x.float() * w``).  The kernel reads the weights when it runs: a kernel
+    that wrote them earlier on the same stream is seen, nothing synchronises,
+    and a captured graph replays with the values the tensor then holds.  They
+    are not validated and must not overlap ``out``.
     """
     _check_tensor(out, "out")
     if count is None:
@@ -240,16 +274,19 @@ def reduce_widened(out, inputs, count=None, stream=None, config=None, scale=None
     _check_widened(in_dtype, out.dtype)
     if out.numel() < count:
         raise ValueError(f"hiccl: out has {out.numel()} < count={count} elements")
+    if weights is not None:
+        _check_weights(weights, len(ptrs), out, out.data_ptr(), count)
     with torch.cuda.device(out.device):  # the library launches on the current device
         reduce_widened_ptrs(L.DTYPE_OF_TORCH[in_dtype], out.data_ptr(), ptrs, count,
                             stream=_stream_handle(stream, out.device).value or 0, config=config, scale=scale,
-                            accumulate=accumulate)
+                            accumulate=accumulate, weights=weights)
     return out
 
 
 def reduce_widened_ptrs(in_dtype_code, out_ptr, in_ptrs, count, stream=None, config=None, scale=None,
-                        out_dtype_code=L.HICCL_FLOAT32, accumulate=False):
-    """Raw-pointer form of :func:`reduce_widened` (pointers already offset)."""
+                        out_dtype_code=L.HICCL_FLOAT32, accumulate=False, weights=None):
+    """Raw-pointer form of :func:`reduce_widened` (pointers already offset);
+    ``weights`` is a tensor here too."""
     _check_accumulate(accumulate)
     _check_widened(in_dtype_code, out_dtype_code)
     _check_widened_config(config)
@@ -258,6 +295,13 @@ def reduce_widened_ptrs(in_dtype_code, out_ptr, in_ptrs, count, stream=None, con
         alpha = ctypes.byref(ctypes.c_double(_check_scale(scale, in_dtype_code)))
     tab = _ptr_table(list(in_ptrs))
     cfg = ctypes.byref(L.ReduceConfig(**config)) if config is not None else None
+    if weights is not None:
+        w0 = _check_weights(weights, len(in_ptrs), None, out_ptr, count)
+        rc = L.lib().hiccl_reduce_weighted(int(in_dtype_code), int(out_dtype_code), alpha, 1 if accumulate else 0,
+                                           ctypes.c_void_p(out_ptr), tab, ctypes.c_void_p(w0), len(in_ptrs), count,
+                                           _stream_handle(stream), cfg)
+        L.check(rc, "hiccl_reduce_weighted")
+        return
     fn = L.lib().hiccl_reduce_accumulate if accumulate else L.lib().hiccl_reduce_widened
     rc = fn(int(in_dtype_code), int(out_dtype_code), alpha, ctypes.c_void_p(out_ptr), tab, len(in_ptrs), count,
             _stream_handle(stream), cfg)
@@ -284,7 +328,7 @@ def bucket(n, count, dtype=torch.float32, device=None):
 
 
 def auto_choice(dtype, count, n, config=None, cus=256, op=L.HICCL_OP_SUM, scale=False, out_dtype=None,
-                accumulate=False):
+                accumulate=False, weighted=False):
     """What a one-shot call (and a one-compute plan at TILE unroll 2 / 4 or
     AUTO) resolves to on a GPU of ``cus`` CUs, without a device:
     ``hiccl_reduce_auto_choice_ex`` (``op`` other than SUM:
@@ -296,8 +340,12 @@ def auto_choice(dtype, count, n, config=None, cus=256, op=L.HICCL_OP_SUM, scale=
     ``out_dtype`` (torch.float32 with a bf16, f16 or FP8 ``dtype``): a widened
     sum, ``hiccl_reduce_auto_choice_widened`` -- the same answer scaled or not;
     with ``accumulate=True`` ``hiccl_reduce_auto_choice_accumulate``, the same
-    answer again."""
+    answer again.  ``weighted=True`` (with ``out_dtype``):
+    ``hiccl_reduce_auto_choice_weighted``, which answers what the unweighted
+    entry of the same ``accumulate`` answers."""
     _check_accumulate(accumulate, out_dtype is not None)
+    if weighted and out_dtype is None:
+        raise ValueError("hiccl: only a widened sum is weighted: weighted=True goes with out_dtype=torch.float32")
     dt = L.DTYPE_OF_TORCH[dtype] if isinstance(dtype, torch.dtype) else int(dtype)
     cfg = ctypes.byref(L.ReduceConfig(**config)) if config else None
     out = [ctypes.c_int() for _ in range(5)]
@@ -306,8 +354,13 @@ def auto_choice(dtype, count, n, config=None, cus=256, op=L.HICCL_OP_SUM, scale=
         if op != L.HICCL_OP_SUM:
             raise ValueError("hiccl: only sums are widened: out_dtype= goes with HICCL_OP_SUM")
         _check_widened_config(config)
-        fn = L.lib().hiccl_reduce_auto_choice_accumulate if accumulate else L.lib().hiccl_reduce_auto_choice_widened
-        rc = fn(dt, cfg, count, float(n), cus, *[ctypes.byref(v) for v in out])
+        if weighted:
+            rc = L.lib().hiccl_reduce_auto_choice_weighted(dt, 1 if accumulate else 0, cfg, count, float(n), cus,
+                                                           *[ctypes.byref(v) for v in out])
+        else:
+            fn = (L.lib().hiccl_reduce_auto_choice_accumulate if accumulate
+                  else L.lib().hiccl_reduce_auto_choice_widened)
+            rc = fn(dt, cfg, count, float(n), cus, *[ctypes.byref(v) for v in out])
     elif scale:
         _check_scale(1.0, dtype if isinstance(dtype, torch.dtype) else dt, op)
         rc = L.lib().hiccl_reduce_auto_choice_scaled(dt, cfg, count, float(n), cus, *[ctypes.byref(v) for v in out])
@@ -336,8 +389,10 @@ class Compute:
 
     def __init__(self, dtype=torch.float32, device=None, myid=0, acc=L.HICCL_ACC_NATIVE,
                  engine=L.HICCL_ENGINE_AUTO, config=None, op=L.HICCL_OP_SUM, scale=None, out_dtype=None,
-                 accumulate=False):
+                 accumulate=False, weighted=False):
         _check_accumulate(accumulate, out_dtype is not None)
+        if weighted and out_dtype is None:
+            raise ValueError("hiccl: only a widened plan is weighted: weighted=True goes with out_dtype=torch.float32")
         self.dtype = dtype
         self.code = L.DTYPE_OF_TORCH[dtype]
         if scale is not None:
@@ -374,10 +429,17 @@ class Compute:
         if out_dtype is not None:
             L.check(L.lib().hiccl_reduce_plan_set_out_dtype(self._plan, L.DTYPE_OF_TORCH[out_dtype]),
                     "plan_set_out_dtype")
+        if weighted:  # before the first add, as the output dtype
+            L.check(L.lib().hiccl_reduce_plan_set_weighted(self._plan, 1), "plan_set_weighted")
         if scale is not None:
             self.set_scale(scale)
         if accumulate:
             self.set_accumulate(True)
+
+    def weighted(self):
+        """Is the plan weighted (hiccl_reduce_plan_weighted: ``weighted=True``
+        at construction)?  Every add then brings ``weights=``."""
+        return L.lib().hiccl_reduce_plan_weighted(self._plan) == 1
 
     def set_accumulate(self, on):
         """Accumulation of a widened plan (hiccl_reduce_plan_set_accumulate):
@@ -469,26 +531,39 @@ class Compute:
             t, off = buf, 0
         return t, t.data_ptr() + off * esz
 
-    def add(self, inputbuf, outputbuf, count, compid, unscaled=False):
+    def add(self, inputbuf, outputbuf, count, compid, unscaled=False, weights=None):
         """Register one compute on its owning rank.  ``unscaled``: in a plan
         that has a scale this compute writes the plain sum
         (hiccl_reduce_plan_add_unscaled: an intermediate compute of a
         hierarchical average); without a scale it changes nothing.  A widened
-        or accumulating plan takes none."""
+        or accumulating plan takes none.  ``weights``: on a weighted plan
+        (``weighted=True``) the compute's f32 weights, one per input, a
+        contiguous float32 tensor on the plan's device
+        (hiccl_reduce_plan_add_weighted); the plan keeps the tensor and every
+        launch reads the values it then holds."""
         if self.myid != compid:
             return
+        if weights is None and self.weighted():
+            raise ValueError("hiccl: a weighted plan takes weighted computes only: add(..., weights=tensor)")
+        if weights is not None and not self.weighted():
+            raise ValueError("hiccl: the plan is not weighted: Compute(..., out_dtype=torch.float32, weighted=True)")
         if unscaled and self.out_dtype != self.dtype:
             raise ValueError("hiccl: a widened or accumulating plan takes no unscaled compute (one scale per plan)")
         esz = L.lib().hiccl_dtype_size(self.code)
         ins = [self._ptr(b, esz) for b in inputbuf]
         ot, op = self._ptr(outputbuf, L.lib().hiccl_dtype_size(L.DTYPE_OF_TORCH[self.out_dtype]))
         tab = _ptr_table([p for _, p in ins])
-        fn = L.lib().hiccl_reduce_plan_add_unscaled if unscaled else L.lib().hiccl_reduce_plan_add
-        L.check(fn(self._plan, ctypes.c_void_p(op), tab, len(ins), count),
-                "plan_add_unscaled" if unscaled else "plan_add")
+        if weights is not None:
+            w0 = _check_weights(weights, len(ins), ot, op, count)
+            L.check(L.lib().hiccl_reduce_plan_add_weighted(self._plan, ctypes.c_void_p(op), tab, ctypes.c_void_p(w0),
+                                                           len(ins), count), "plan_add_weighted")
+        else:
+            fn = L.lib().hiccl_reduce_plan_add_unscaled if unscaled else L.lib().hiccl_reduce_plan_add
+            L.check(fn(self._plan, ctypes.c_void_p(op), tab, len(ins), count),
+                    "plan_add_unscaled" if unscaled else "plan_add")
         if count == 0:  # validated, then dropped by the plan (a no-op): numcomp is hiccl_reduce_plan_numcomp
             return
-        self._keep.append((ot, [t for t, _ in ins]))
+        self._keep.append((ot, [t for t, _ in ins], weights))
         self.inputbuf.append([p for _, p in ins])
         self.outputbuf.append(op)
         self.count.append(count)

@@ -987,6 +987,63 @@ typedef OpWidenAccum<WidenBF16> OpBF16AccF32;
 typedef OpWidenAccum<WidenF16> OpF16AccF32;
 template <int FMT> using OpF8AccF32 = OpWidenAccum<WidenF8<FMT>>;
 
+// --------------------------------------------------- weighted widened sums --
+// out = finish(((+0 + fl32(w[0] * widen(x[0]))) + fl32(w[1] * widen(x[1]))) + ...)
+// (hiccl_reduce_weighted, hiccl_reduce_plan_set_weighted): the widened sum, or
+// the accumulating one, of inputs that each count with an f32 weight of their
+// own -- NCCL's PreMulSum.  The weights live in DEVICE memory and are read when
+// the kernel runs (weight_of: scalar loads through the constant address space,
+// so a weight stays in an SGPR and is one operand of the lanes' multiplies).
+// The multiply and the add are TWO separately rounded f32 operations: the
+// products pass through an empty asm (opaque_f32x4 / opaque_f32), so they cannot
+// contract with the add that follows into v_fma_f32 / v_pk_fma_f32 (a
+// different word: one rounding less).  A weight of exactly 1.0f gives
+// t = widen(x) bit for bit, so all-ones weights give the widened sum's words.
+// zero(), pack() and sstore() are the base family's: alpha, the old output and
+// n = 0 behave as they do there.
+// An op of this family sets kWeighted; its add() and sadd() take the weight,
+// which the engines fetch from the Inputs functor (w(k)) behind if constexpr.
+// Families of their own, with kernels of their own (k_reduce_single_weighted,
+// k_reduce_plan_weighted): every other kernel stays what it is.
+template <class Op, class = void>
+struct weighted : std::false_type {};
+template <class Op>
+struct weighted<Op, std::enable_if_t<Op::kWeighted>> : std::true_type {};
+
+// what the engines carry per input next to its packets: the weight, or nothing
+struct NoWeight {};
+template <class Op> using w_t = std::conditional_t<weighted<Op>::value, float, NoWeight>;
+
+template <class Op, class Inputs>
+__device__ __forceinline__ w_t<Op> weight_of(const Inputs &in, uint32_t k) {
+  if constexpr (weighted<Op>::value) return in.w(k);
+  else return {};
+}
+template <class Op>
+__device__ __forceinline__ typename Op::acc_t add_in(typename Op::acc_t a, in_pkt_t<Op> x, w_t<Op> w) {
+  if constexpr (weighted<Op>::value) return Op::add(a, x, w);
+  else return Op::add(a, x);
+}
+
+__device__ __forceinline__ f32x4 opaque_f32x4(f32x4 x) {
+  asm("" : "+v"(x));
+  return x;
+}
+
+template <class W>
+struct OpWeighted : OpWiden<W> {
+  static constexpr bool kWeighted = true;
+  __device__ static f32x4 add(f32x4 a, typename W::in_t p, float w) { return a + opaque_f32x4(W::widen4(p) * w); }
+  __device__ static float sadd(float a, const char *p, float w) { return a + opaque_f32(W::ld(p) * w); }
+};
+
+template <class W>
+struct OpWeightedAccum : OpWidenAccum<W> {
+  static constexpr bool kWeighted = true;
+  __device__ static f32x4 add(f32x4 a, typename W::in_t p, float w) { return a + opaque_f32x4(W::widen4(p) * w); }
+  __device__ static float sadd(float a, const char *p, float w) { return a + opaque_f32(W::ld(p) * w); }
+};
+
 // The old output packets of a unit, one buffer_load_dwordx4 each (kAccum ops).
 template <class Op, int U, int POL>
 __device__ __forceinline__ void load_old(u32x4 (&old)[U], rsrc_t w, const uint32_t (&voff)[U]) {
@@ -1008,6 +1065,17 @@ struct ArgInputs {
   __device__ const char *operator()(int k) const { return p[k]; }
 };
 
+// The weights of a weighted op (engine.h's weighted sums): n consecutive floats
+// in device memory, read through the constant address space (4) as the plan's
+// pointer table is (TableInputs) -- scalar loads, the value known uniform.  Only
+// a weighted op's kernels build these functors and only its add()s call w().
+typedef const float __attribute__((address_space(4))) ConstF32;
+
+struct ArgInputsWeighted : ArgInputs {
+  const float *wp;
+  __device__ float w(int k) const { return ((ConstF32 *)wp)[k]; }
+};
+
 // Under the peer policies the plain scalar accesses are bracketed by
 // system-scope fences instead (an acquire before the loads: this XCD's L2
 // drops lines of peer memory; a release after the stores: its dirty lines
@@ -1022,7 +1090,10 @@ __device__ __forceinline__ void scalar_part(char *out, Inputs in, uint32_t n, ui
   uint64_t e = (tid < (int)head) ? (uint64_t)tid : (uint64_t)head + npkt * V + (tid - head);
   uint64_t off = e * Op::kEsz;
   typename Op::sacc_t acc = Op::szero();
-  for (uint32_t k = 0; k < n; k++) acc = Op::sadd(acc, in(k) + off);
+  for (uint32_t k = 0; k < n; k++) {
+    if constexpr (weighted<Op>::value) acc = Op::sadd(acc, in(k) + off, in.w(k));
+    else acc = Op::sadd(acc, in(k) + off);
+  }
   if constexpr (widens_out<Op>::value) sstore_fin<Op>(out + e * Op::kOutEsz, acc, fin);
   else sstore_fin<Op>(out + off, acc, fin);
   if constexpr (POL / 10 == kPolStoreSys) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
@@ -1051,6 +1122,12 @@ __device__ __forceinline__ void group_at(typename Op::acc_t (&acc)[U], Inputs in
   rsrc_t r[G];
 #pragma unroll
   for (int j = 0; j < G; j++) r[j] = make_rsrc(in(g + j) + in_bytes<Op>(tile_off), in_bytes<Op>(tile_bytes));
+  // a weighted op's G weights, indexed in the input LIST (g + j): scalar loads
+  [[maybe_unused]] float wt[weighted<Op>::value ? G : 1];
+  if constexpr (weighted<Op>::value) {
+#pragma unroll
+    for (int j = 0; j < G; j++) wt[j] = in.w(g + j);
+  }
   in_pkt_t<Op> x[G][U];
   // Every load of the group is issued before the first add, input by input
   // (the barriers pin that order, so the adds -- input 0 first -- wait with
@@ -1073,7 +1150,10 @@ __device__ __forceinline__ void group_at(typename Op::acc_t (&acc)[U], Inputs in
 #pragma unroll
   for (int j = 0; j < G; j++) {
 #pragma unroll
-    for (int u = 0; u < U; u++) acc[u] = Op::add(acc[u], x[j][u]);
+    for (int u = 0; u < U; u++) {
+      if constexpr (weighted<Op>::value) acc[u] = Op::add(acc[u], x[j][u], wt[j]);
+      else acc[u] = Op::add(acc[u], x[j][u]);
+    }
   }
 }
 
@@ -1200,6 +1280,9 @@ __device__ __forceinline__ void chunk_body(char *outb, Inputs in, uint32_t n, ui
     in_pkt_t<Op> x[P], y[P];
     const uint64_t ioff = in_bytes<Op>(off);
     const uint32_t ibytes = in_bytes<Op>(nbytes);
+    // a weighted op's weights travel with the packets they belong to (wx with
+    // x, wy with y): scalar loads, indexed in the input list like the pointers
+    [[maybe_unused]] w_t<Op> wx = weight_of<Op>(in, 0), wy = {};
     {
       rsrc_t r = make_rsrc(in(0) + ioff, ibytes);
 #pragma unroll
@@ -1211,18 +1294,20 @@ __device__ __forceinline__ void chunk_body(char *outb, Inputs in, uint32_t n, ui
     uint32_t j = 0;
     for (; j + 2 <= n; j += 2) {  // x: input j in flight
       rsrc_t ry = make_rsrc(in(j + 1) + ioff, ibytes);
+      wy = weight_of<Op>(in, j + 1);
 #pragma unroll
       for (int p = 0; p < P; p++) y[p] = load_in<Op, POL>(ry, voff[p]);
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int p = 0; p < P; p++) {
-        acc[p] = Op::add(acc[p], x[p]);
+        acc[p] = add_in<Op>(acc[p], x[p], wx);
         pin_acc<Op>(acc[p]);
         if constexpr (Op::kWidens) __builtin_amdgcn_sched_barrier(0);
       }
       __builtin_amdgcn_sched_barrier(0);
       const bool more = j + 2 < n;
       rsrc_t rx = make_rsrc(in(more ? j + 2 : j + 1) + ioff, more ? ibytes : 0u);
+      wx = weight_of<Op>(in, more ? j + 2 : j + 1);
 #pragma unroll
       for (int p = 0; p < P; p++) x[p] = load_in<Op, POL>(rx, voff[p]);
       if constexpr (accumulates<Op>::value) {
@@ -1231,7 +1316,7 @@ __device__ __forceinline__ void chunk_body(char *outb, Inputs in, uint32_t n, ui
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int p = 0; p < P; p++) {
-        acc[p] = Op::add(acc[p], y[p]);
+        acc[p] = add_in<Op>(acc[p], y[p], wy);
         pin_acc<Op>(acc[p]);
         if constexpr (Op::kWidens) __builtin_amdgcn_sched_barrier(0);
       }
@@ -1239,7 +1324,7 @@ __device__ __forceinline__ void chunk_body(char *outb, Inputs in, uint32_t n, ui
     }
     if (n & 1) {
 #pragma unroll
-      for (int p = 0; p < P; p++) acc[p] = Op::add(acc[p], x[p]);
+      for (int p = 0; p < P; p++) acc[p] = add_in<Op>(acc[p], x[p], wx);
     }
   } else if constexpr (accumulates<Op>::value) {
     load_old<Op, P, POL>(old, wo, voff);  // n == 0: out = p + (+0), or p + a zero of alpha's sign
@@ -1302,6 +1387,7 @@ struct Shifted {
   Inner in;
   uint64_t shift;
   __device__ const char *operator()(int k) const { return in(k) + shift; }
+  __device__ float w(int k) const { return in.w(k); }  // a weight belongs to its input, wherever the body starts
 };
 
 // ---------------------------------------------------- unit scheduling ----
@@ -1447,6 +1533,11 @@ struct TableInputs {
   __device__ const char *operator()(int k) const { return ((ConstPtr *)p)[k]; }
 };
 
+struct TableInputsWeighted : TableInputs {
+  const float *wp;
+  __device__ float w(int k) const { return ((ConstF32 *)wp)[k]; }
+};
+
 typedef const PlanDesc __attribute__((address_space(4))) ConstDesc;
 typedef const uint32_t __attribute__((address_space(4))) ConstU32;
 
@@ -1561,6 +1652,65 @@ __global__ __launch_bounds__(BLOCK) void k_reduce_plan_mixed(PlanArgsScaled a) {
     }
     const uint64_t shift = (uint64_t)d.head * Op::kEsz;
     Shifted<TableInputs> in{raw, shift};
+    const uint64_t left = d.npkt - pkt0;
+    const uint32_t tile_bytes = (uint32_t)((left < TILE ? left : TILE) * kPacket);
+    unit_body<Op, U, POL, ENG>(d.out + (uint64_t)d.head * out_esz<Op>(), in, d.n, pkt0 * kPacket, tile_bytes, voff, hook,
+                               fin);
+  });
+}
+
+// The weighted sums' kernels (OpWeighted, OpWeightedAccum): the scaled kernels'
+// bodies over inputs that carry their weights -- the one-shot kernel takes the
+// weight pointer behind the scaled kernel's arguments, the plan kernel a device
+// table of one weight pointer per compute (read with the compute's descriptor:
+// scalar loads).  Head, body and tail of a compute read the same n floats.
+// Bodies of their own, as the three above and for their reason.
+template <class Op, int BLOCK, int U, int POL, int ENG>
+__global__ __launch_bounds__(BLOCK) void k_reduce_single_weighted(SingleArgsWeighted a) {
+  const fin_t<Op> fin = Op::fin(a.scale);
+  const int tid = threadIdx.x;
+  uint32_t voff[U];
+#pragma unroll
+  for (int u = 0; u < U; u++) voff[u] = (uint32_t)((u * BLOCK + tid) * kPacket);
+  ArgInputsWeighted raw{{a.in}, a.weights};
+  if (blockIdx.x == 0) scalar_part<Op>(a.out, raw, a.n, a.head, a.npkt, a.tail, tid, fin);
+  if (a.npkt == 0) return;  // (the host never passes a sched counter then)
+  const uint64_t shift = (uint64_t)a.head * Op::kEsz;
+  Shifted<ArgInputsWeighted> in{raw, shift};
+  char *outb = a.out + (uint64_t)a.head * out_esz<Op>();
+  constexpr uint64_t TILE = (uint64_t)BLOCK * U;
+  for_each_unit(a.sched, a.grab, 0, a.ntiles, [&](uint64_t u, auto hook) {
+    const uint64_t t = tile_order(u, a.ntiles, a.order);
+    const uint64_t pkt0 = t * TILE;
+    const uint64_t left = a.npkt - pkt0;
+    const uint32_t tile_bytes = (uint32_t)((left < TILE ? left : TILE) * kPacket);
+    unit_body<Op, U, POL, ENG, decltype(hook)::kDynamic>(outb, in, a.n, pkt0 * kPacket, tile_bytes, voff, hook, fin);
+  }, a.drain);
+}
+
+typedef const float *const __attribute__((address_space(4))) ConstWeightPtr;
+
+template <class Op, int BLOCK, int U, int POL, int ENG>
+__global__ __launch_bounds__(BLOCK) void k_reduce_plan_weighted(PlanArgsWeighted a) {
+  const fin_t<Op> fin = Op::fin(a.scale);
+  const int tid = threadIdx.x;
+  uint32_t voff[U];
+#pragma unroll
+  for (int u = 0; u < U; u++) voff[u] = (uint32_t)((u * BLOCK + tid) * kPacket);
+  constexpr uint64_t TILE = (uint64_t)BLOCK * U;
+  for_each_unit(a.sched, a.grab, a.t_begin, a.t_end, [&](uint64_t t, auto hook) {
+    const uint32_t c = a.unit_comp ? ((ConstU32 *)a.unit_comp)[t] : 0u;
+    const PlanDesc d = load_desc(a.desc, c);
+    const uint64_t lt = t - d.tile_begin;
+    TableInputsWeighted raw{{a.ptrs + (uint64_t)c * a.stride}, ((ConstWeightPtr *)a.weights)[c]};
+    if (lt == 0) scalar_part<Op, POL>(d.out, raw, d.n, d.head, d.npkt, d.tail, tid, fin);
+    const uint64_t pkt0 = lt * TILE;
+    if (pkt0 >= d.npkt) {  // a scalar-only compute: nothing to load or store
+      hook();
+      return;
+    }
+    const uint64_t shift = (uint64_t)d.head * Op::kEsz;
+    Shifted<TableInputsWeighted> in{raw, shift};
     const uint64_t left = d.npkt - pkt0;
     const uint32_t tile_bytes = (uint32_t)((left < TILE ? left : TILE) * kPacket);
     unit_body<Op, U, POL, ENG>(d.out + (uint64_t)d.head * out_esz<Op>(), in, d.n, pkt0 * kPacket, tile_bytes, voff, hook,
@@ -1910,6 +2060,33 @@ R with_elem_accum(int dtype, int acc, R unknown, F f) {
   }
 }
 
+// Weighted widened sums (kOpWeightedSum, kOpWeightedAccum): the same list with
+// the weighted ops.  Untuned; a list of its own, not a part of with_elem -- its
+// kernels have argument structs and launcher types of their own.
+template <class R, class F>
+R with_elem_weighted(int dtype, int acc, int op, R unknown, F f) {
+  if (acc != HICCL_ACC_NATIVE) return unknown;
+  if (op == kOpWeightedSum) {
+    switch (dtype) {
+      case HICCL_BFLOAT16: return f(Elem<HICCL_BFLOAT16, OpWeighted<WidenBF16>, false>());
+      case HICCL_FLOAT16: return f(Elem<HICCL_FLOAT16, OpWeighted<WidenF16>, false>());
+      case HICCL_FLOAT8_E4M3: return f(Elem<HICCL_FLOAT8_E4M3, OpWeighted<WidenF8<kE4M3>>, false>());
+      case HICCL_FLOAT8_E5M2: return f(Elem<HICCL_FLOAT8_E5M2, OpWeighted<WidenF8<kE5M2>>, false>());
+      default: return unknown;
+    }
+  }
+  if (op == kOpWeightedAccum) {
+    switch (dtype) {
+      case HICCL_BFLOAT16: return f(Elem<HICCL_BFLOAT16, OpWeightedAccum<WidenBF16>, false>());
+      case HICCL_FLOAT16: return f(Elem<HICCL_FLOAT16, OpWeightedAccum<WidenF16>, false>());
+      case HICCL_FLOAT8_E4M3: return f(Elem<HICCL_FLOAT8_E4M3, OpWeightedAccum<WidenF8<kE4M3>>, false>());
+      case HICCL_FLOAT8_E5M2: return f(Elem<HICCL_FLOAT8_E5M2, OpWeightedAccum<WidenF8<kE5M2>>, false>());
+      default: return unknown;
+    }
+  }
+  return unknown;
+}
+
 template <int PART, class R, class F>
 R with_elem(int dtype, int acc, int op, R unknown, F f) {
   if constexpr (PART == kPartMixed) {  // the scaled ops themselves, FP8's included
@@ -2128,6 +2305,53 @@ plan_fn pick_plan_mixed_eng(int engine, int unroll, int pol) {
     case 10 * kPolStoreSys + L: return pick_plan_mixed_pol<Op, 10 * kPolStoreSys + L>(engine, unroll);
     case 10 * S + kPolLoadSys: return pick_plan_mixed_pol<Op, 10 * S + kPolLoadSys>(engine, unroll);
     case 10 * kPolStoreSys + kPolLoadSys: return pick_plan_mixed_pol<Op, 10 * kPolStoreSys + kPolLoadSys>(engine, unroll);
+    default: return nullptr;
+  }
+}
+
+// The weighted kernels (k_reduce_single_weighted, k_reduce_plan_weighted): the
+// shapes the widened and accumulating families have -- one-shot: either
+// engine's default shape with nt or write-through stores; plan: either engine's
+// default shape under the four plan policies -- and no tuning table.
+template <class Op, int B, int U, int POL, int ENG>
+void launch_single_weighted_t(const SingleArgsWeighted &a, dim3 grid, hipStream_t s) {
+  hipLaunchKernelGGL((k_reduce_single_weighted<Op, B, U, POL, ENG>), grid, dim3(B), 0, s, a);
+}
+
+template <class Op>
+single_w_fn pick_single_weighted_op(int engine, int block, int unroll, int pol) {
+  constexpr int WT = 10 * kPolStoreSys + 1;
+  if (engine == HICCL_ENGINE_PHASE) {
+    constexpr int PD = phase_p_of<Op>();
+    if (block != kPhBlock || unroll != PD) return nullptr;
+    if (pol == WT) return launch_single_weighted_t<Op, kPhBlock, PD, WT, kPhase>;
+    return pol == kDefPol ? launch_single_weighted_t<Op, kPhBlock, PD, kDefPol, kPhase> : nullptr;
+  }
+  if (block != kDefBlock || unroll != kDefUnroll) return nullptr;
+  if (pol == WT) return launch_single_weighted_t<Op, kDefBlock, kDefUnroll, WT, kTile>;
+  return pol == kDefPol ? launch_single_weighted_t<Op, kDefBlock, kDefUnroll, kDefPol, kTile> : nullptr;
+}
+
+template <class Op, int ENG, int U, int POL>
+void launch_plan_weighted_t(const PlanArgsWeighted &a, dim3 grid, hipStream_t s) {
+  constexpr int B = ENG == kPhase ? kPhBlock : kDefBlock;
+  hipLaunchKernelGGL((k_reduce_plan_weighted<Op, B, U, POL, ENG>), grid, dim3(B), 0, s, a);
+}
+
+template <class Op, int POL>
+plan_w_fn pick_plan_weighted_pol(int engine, int unroll) {
+  if (engine == HICCL_ENGINE_PHASE) return launch_plan_weighted_t<Op, kPhase, phase_p_of<Op>(), POL>;
+  return unroll == 0 || unroll == kDefUnroll ? launch_plan_weighted_t<Op, kTile, kDefUnroll, POL> : nullptr;
+}
+
+template <class Op>
+plan_w_fn pick_plan_weighted_eng(int engine, int unroll, int pol) {
+  constexpr int L = kDefPol % 10, S = kDefPol / 10;
+  switch (pol) {
+    case kDefPol: return pick_plan_weighted_pol<Op, kDefPol>(engine, unroll);
+    case 10 * kPolStoreSys + L: return pick_plan_weighted_pol<Op, 10 * kPolStoreSys + L>(engine, unroll);
+    case 10 * S + kPolLoadSys: return pick_plan_weighted_pol<Op, 10 * S + kPolLoadSys>(engine, unroll);
+    case 10 * kPolStoreSys + kPolLoadSys: return pick_plan_weighted_pol<Op, 10 * kPolStoreSys + kPolLoadSys>(engine, unroll);
     default: return nullptr;
   }
 }

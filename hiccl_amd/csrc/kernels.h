@@ -57,7 +57,22 @@ constexpr int kOpWidenSum = 0x101;
 // f32 output and add the (scaled) sum to it.  Everything said of kOpWidenSum
 // holds; is_widen_op answers for both.
 constexpr int kOpWidenAccum = 0x102;
-constexpr bool is_widen_op(int op) { return op == kOpWidenSum || op == kOpWidenAccum; }
+// A weighted widened sum (hiccl_reduce_weighted, hiccl_reduce_plan_set_weighted):
+// a widened sum, or an accumulating one, whose inputs each count with an f32
+// weight read from device memory when the kernel runs.  Everything said of
+// kOpWidenSum / kOpWidenAccum holds and is_widen_op answers for them too; their
+// kernels take the weights behind the scaled kernels' arguments
+// (SingleArgsWeighted, PlanArgsWeighted) and have launcher types of their own.
+constexpr int kOpWeightedSum = 0x104;
+constexpr int kOpWeightedAccum = 0x105;
+constexpr bool is_weighted_op(int op) { return op == kOpWeightedSum || op == kOpWeightedAccum; }
+constexpr bool is_widen_op(int op) { return op == kOpWidenSum || op == kOpWidenAccum || is_weighted_op(op); }
+// does the op read the old output (the accumulating families)?
+constexpr bool is_accum_op(int op) { return op == kOpWidenAccum || op == kOpWeightedAccum; }
+// the unweighted family an op belongs to: its thresholds, its bytes, its PHASE chunk unless phase_p says otherwise
+constexpr int unweighted_op(int op) {
+  return op == kOpWeightedSum ? kOpWidenSum : op == kOpWeightedAccum ? kOpWidenAccum : op;
+}
 // A scaled plan in which some computes, not all, write the plain sum
 // (hiccl_reduce_plan_add_unscaled: the intermediate computes of an averaging
 // Comm<T> step): the MIXED plan kernels, which read the choice per compute from
@@ -126,6 +141,19 @@ struct PlanArgsScaled : PlanArgs {  // as SingleArgsScaled
   Scale scale;
 };
 
+// The weighted sums' kernels (k_reduce_single_weighted, k_reduce_plan_weighted)
+// take the weights behind the scaled kernels' arguments, whose own structs stay
+// as they are: n consecutive floats in device memory for a one-shot call (the
+// caller's pointer), one such pointer per compute for a plan (a device table
+// behind the plan's descriptor table).
+struct SingleArgsWeighted : SingleArgsScaled {
+  const float *weights;
+};
+
+struct PlanArgsWeighted : PlanArgsScaled {
+  const float *const *weights;  // weights[c]: compute c's n floats
+};
+
 constexpr int kMaxFlags = 64;  // signal and wait flags per launch (one per lane)
 
 // Several signal/wait phases in ONE launch, executed in order: phase p
@@ -182,7 +210,8 @@ size_t esize(int dtype);            // bytes per element, 0 for an unknown dtype
 // a headline type (f32, bf16 / f16 native) under SUM: the full tuning table
 bool tuned_type(int dtype, int acc, int op);
 // packets per lane of the PHASE engine's default chunk: a property of (dtype,
-// acc) under every operator but kOpWidenAccum, which takes 8.  The operator is
+// acc) under every operator but kOpWidenAccum, which takes 8, and the weighted
+// ops, which answer for themselves (phase_p_weighted).  The operator is
 // not defaulted: a caller that sizes units (unit_pkts) must name the launch's
 // own, or the descriptor table and the kernel disagree about the chunk.
 int phase_p(int dtype, int acc, int op);
@@ -221,6 +250,14 @@ single_fn pick_single_accum(int dtype, int acc, int op, int engine, int block, i
 plan_fn pick_plan_accum(int dtype, int acc, int op, int engine, int unroll, int pol);
 // the mixed plan kernels (reduce_mixed.hip; op == kOpMixedSum, the six floating dtypes): plan kernels only
 plan_fn pick_plan_mixed(int dtype, int acc, int op, int engine, int unroll, int pol);
+// the weighted widened sums (reduce_weighted.hip; op == kOpWeightedSum / kOpWeightedAccum, dtype: the inputs'):
+// launchers of their own type, either engine's default shape, no program kernels; phase_p asks
+// phase_p_weighted for their PHASE chunk
+typedef void (*single_w_fn)(const SingleArgsWeighted &, dim3, hipStream_t);
+typedef void (*plan_w_fn)(const PlanArgsWeighted &, dim3, hipStream_t);
+single_w_fn pick_single_weighted(int dtype, int acc, int op, int engine, int block, int unroll, int pol);
+plan_w_fn pick_plan_weighted(int dtype, int acc, int op, int engine, int unroll, int pol);
+int phase_p_weighted(int dtype, int op);
 
 // ---- the plain kernels
 

@@ -21,11 +21,14 @@ uint32_t log2u(int v) {
 
 // Large-n one-shot path: stage the pointer table in stream-ordered device
 // memory and run it as a one-compute plan.
+// A weighted sum's one weight pointer -- the caller's, passed along, not copied
+// -- goes behind the table (PlanArgsWeighted.weights).
 int reduce_via_table(int dtype, const Cfg &c, const Scale &scale, void *out, const void *const *in, int n,
-                     size_t count, hipStream_t s) {
+                     size_t count, hipStream_t s, const float *weights) {
   DescTable t((size_t)n, unit_pkts(c.engine, dtype, c.acc, c.unroll, c.op));
   t.add(out, in, (size_t)n, count, out_esize(dtype, c.op));
-  const std::vector<char> host = t.image();
+  std::vector<char> host = t.image(is_weighted_op(c.op) ? sizeof(weights) : 0);
+  if (is_weighted_op(c.op)) memcpy(host.data() + t.bytes(), &weights, sizeof(weights));
   char *dmem = nullptr;
   if (int e = check_hip(hipMallocAsync((void **)&dmem, host.size(), s), "hiccl_reduce: hipMallocAsync")) return e;
   // hipMemcpyAsync from pageable memory returns once the source is consumed,
@@ -35,12 +38,13 @@ int reduce_via_table(int dtype, const Cfg &c, const Scale &scale, void *out, con
     (void)hipFreeAsync(dmem, s);
     return e;
   }
-  PlanArgsScaled a;
+  PlanArgsWeighted a;
   memset(&a, 0, sizeof(a));
   t.bind(a, dmem);
   a.t_begin = 0;
   a.t_end = t.units;
   a.scale = scale;
+  if (is_weighted_op(c.op)) a.weights = (const float *const *)(dmem + t.bytes());
   // the store form oneshot_cfg decided: write-through by size or on request
   // (store_policy 4), else nt
   const int pol = plan_pol(c.store == kPolStoreSys ? HICCL_PEER_STORES : 0);
@@ -74,6 +78,18 @@ bool widen_in_dtype(int dtype) {
   return dtype == HICCL_BFLOAT16 || dtype == HICCL_FLOAT16 || dtype == HICCL_FLOAT8_E4M3 || dtype == HICCL_FLOAT8_E5M2;
 }
 
+int check_weights(const void *out, const float *weights, int n, size_t count, const std::string &who) {
+  if (n <= 0) return 0;  // nothing reads them: NULL is fine
+  if (!weights) return fail(hipErrorInvalidValue, who + ": weights is NULL (n floats in device memory, one per input)");
+  if ((uintptr_t)weights % sizeof(float))
+    return fail(hipErrorInvalidValue, who + ": weights must be 4-byte aligned");
+  const uintptr_t w0 = (uintptr_t)weights, w1 = w0 + (size_t)n * sizeof(float);
+  const uintptr_t o0 = (uintptr_t)out, o1 = o0 + count * sizeof(float);
+  if (count && w0 < o1 && o0 < w1)
+    return fail(hipErrorInvalidValue, who + ": the weights overlap the output (the kernels read them while they write it)");
+  return 0;
+}
+
 int check_widened(int in_dtype, int out_dtype, int acc, const double *alpha, const std::string &who, Scale *scale) {
   if (out_dtype != HICCL_FLOAT32)
     return fail(hipErrorInvalidValue, who + ": a widened sum writes HICCL_FLOAT32 only (out_dtype " +
@@ -94,14 +110,17 @@ int check_widened(int in_dtype, int out_dtype, int acc, const double *alpha, con
 // hiccl_reduce_scaled (op == kOpScaledSum), hiccl_reduce_widened (op ==
 // kOpWidenSum: `dtype` is the inputs', the output is f32) and
 // hiccl_reduce_accumulate (op == kOpWidenAccum: the same, and the kernels add
-// to the output).
+// to the output).  hiccl_reduce_weighted (op == kOpWeightedSum or
+// kOpWeightedAccum) is either of the last two with `weights`.
 int reduce_call(int dtype, int op, const Scale *scale, void *out, const void *const *in, int n, size_t count,
-                void *stream, const hiccl_reduce_config_t *cfg) {
+                void *stream, const hiccl_reduce_config_t *cfg, const float *weights) {
   const bool widened = is_widen_op(op);
   const size_t esz = out_esize(dtype, op);  // of the OUTPUT: the split, the packets and the bytes written are its
   const Scale sc = scale ? *scale : Scale{0.0, 0.0f, 0u};
   if (widened) {
     if (int e = check_buffers_widened(out, in, n, count, esize(dtype), esz)) return e;
+    if (is_weighted_op(op))
+      if (int e = check_weights(out, weights, n, count, "hiccl_reduce_weighted")) return e;
   }
   if (count == 0) return 0;
   if (dtype == HICCL_BYTES && n != 1) return fail(hipErrorInvalidValue, "hiccl_reduce: HICCL_BYTES copies need n == 1");
@@ -122,11 +141,13 @@ int reduce_call(int dtype, int op, const Scale *scale, void *out, const void *co
     if (capturing(s, false))
       return fail(hipErrorStreamCaptureUnsupported,
                   "hiccl_reduce: n > 64 inputs cannot be captured into a graph (use a plan)");
-    return reduce_via_table(dtype, c, sc, out, in, n, count, s);
+    return reduce_via_table(dtype, c, sc, out, in, n, count, s, weights);
   }
 
-  single_fn fn = single_for(dtype, c);
-  if (!fn)
+  const single_fn fn = is_weighted_op(op) ? nullptr : single_for(dtype, c);
+  const single_w_fn wfn =
+      is_weighted_op(op) ? pick_single_weighted(dtype, c.acc, c.op, c.engine, c.block, c.unroll, c.pol()) : nullptr;
+  if (!fn && !wfn)
     return fail(hipErrorInvalidValue, "hiccl_reduce_ex: unsupported config (block " +
                                           std::to_string(c.block) + ", unroll " +
                                           std::to_string(c.unroll) + ", nt " +
@@ -134,8 +155,9 @@ int reduce_call(int dtype, int op, const Scale *scale, void *out, const void *co
                                           std::to_string(c.store) + ", engine " +
                                           std::to_string(c.engine) + ") for this dtype");
 
-  SingleArgsScaled a;
+  SingleArgsWeighted a;
   memset(&a, 0, sizeof(a));
+  a.weights = weights;
   a.out = (char *)out;
   a.npkt = sp.npkt;
   a.head = sp.head;
@@ -153,7 +175,8 @@ int reduce_call(int dtype, int op, const Scale *scale, void *out, const void *co
   a.grab = L.grab;
   a.drain = (uint32_t)c.drain;
   a.order = log2u(c.order);
-  fn(a, dim3((unsigned)L.grid), s);
+  if (wfn) wfn(a, dim3((unsigned)L.grid), s);
+  else fn(a, dim3((unsigned)L.grid), s);
   return check_hip(hipGetLastError(), "hiccl_reduce: launch");
 }
 
@@ -171,7 +194,7 @@ int auto_choice(int dtype, int op, const hiccl_reduce_config_t *cfg, size_t coun
   const uint64_t npkt = (uint64_t)count * esz / kPacket;
   const Cfg c = oneshot_cfg(dtype, op, cfg, npkt, (uint64_t)count * esz, n, -1);
   // the same refusals as hiccl_reduce_ex: a shape no kernel has is an error
-  const bool has = n > kMaxArgInputs ? plan_shape_error(c, dtype).empty() : single_for(dtype, c) != nullptr;
+  const bool has = n > kMaxArgInputs ? plan_shape_error(c, dtype).empty() : has_single(dtype, c);
   if (!has) return fail(hipErrorInvalidValue, "auto_choice: no kernel for this config and dtype");
   const uint64_t units = tiles_for(npkt, (uint64_t)c.block * c.unroll);  // tiles or phased chunks
   const LaunchShape L = launch_shape(c, n, units, cus, /*paced=*/n <= kMaxArgInputs);
@@ -223,6 +246,26 @@ int hiccl_reduce_auto_choice_accumulate(int in_dtype, const hiccl_reduce_config_
                             "auto_choice_accumulate", nullptr))
     return e;
   return auto_choice(in_dtype, kOpWidenAccum, cfg, count, n, cus, engine, unroll, blocks_per_cu, dynamic, store_policy);
+}
+
+int hiccl_reduce_weighted(int in_dtype, int out_dtype, const double *alpha, int accumulate, void *out,
+                          const void *const *in, const float *weights, int n, size_t count, void *stream,
+                          const hiccl_reduce_config_t *cfg) {
+  Scale sc;
+  if (int e = check_widened(in_dtype, out_dtype, cfg ? cfg->acc : HICCL_ACC_NATIVE, alpha, "hiccl_reduce_weighted", &sc))
+    return e;
+  return reduce_call(in_dtype, accumulate ? kOpWeightedAccum : kOpWeightedSum, &sc, out, in, n, count, stream, cfg,
+                     weights);
+}
+
+int hiccl_reduce_auto_choice_weighted(int in_dtype, int accumulate, const hiccl_reduce_config_t *cfg, size_t count,
+                                      double n, int cus, int *engine, int *unroll, int *blocks_per_cu, int *dynamic,
+                                      int *store_policy) {
+  if (int e = check_widened(in_dtype, HICCL_FLOAT32, cfg ? cfg->acc : HICCL_ACC_NATIVE, nullptr,
+                            "auto_choice_weighted", nullptr))
+    return e;
+  return auto_choice(in_dtype, accumulate ? kOpWeightedAccum : kOpWeightedSum, cfg, count, n, cus, engine, unroll,
+                     blocks_per_cu, dynamic, store_policy);
 }
 
 int hiccl_reduce_auto_choice_widened(int in_dtype, const hiccl_reduce_config_t *cfg, size_t count, double n, int cus,

@@ -46,16 +46,19 @@ bool sync_if_enqueued(std::atomic<bool> &enqueued) {
   return true;
 }
 
-int launch_plan(PlanArgsScaled a, int dtype, const Cfg &c, double mean_n, int dev, hipStream_t s, int pol) {
-  plan_fn fn = pick_plan(dtype, c.acc, c.op, c.engine, c.unroll, pol);
-  if (!fn)
+int launch_plan(PlanArgsWeighted a, int dtype, const Cfg &c, double mean_n, int dev, hipStream_t s, int pol) {
+  const bool weighted = is_weighted_op(c.op);
+  const plan_fn fn = weighted ? nullptr : pick_plan(dtype, c.acc, c.op, c.engine, c.unroll, pol);
+  const plan_w_fn wfn = weighted ? pick_plan_weighted(dtype, c.acc, c.op, c.engine, c.unroll, pol) : nullptr;
+  if (!fn && !wfn)
     return fail(hipErrorInvalidValue, pol == kDefPol ? "plan: unsupported dtype / shape"
                                                      : "plan: no peer-policy kernel for this shape (PHASE default, "
                                                        "TILE unroll 4, f32 / bf16 / f16 also 2)");
   const LaunchShape L = launch_shape(c, mean_n, a.t_end - a.t_begin, device_cus(dev));
   a.grab = L.grab;
   a.sched = L.dynamic ? ticket_counter(dev, s) : nullptr;
-  fn(a, dim3((unsigned)L.grid), s);
+  if (wfn) wfn(a, dim3((unsigned)L.grid), s);
+  else fn(a, dim3((unsigned)L.grid), s);
   return check_hip(hipGetLastError(), "plan: launch");
 }
 
@@ -130,7 +133,12 @@ int plan_upload(hiccl_reduce_plan *p, hipStream_t s) {
   // (the flag is read by the mixed kernels alone: every other plan kernel takes pad for zero)
   for (auto &cp : p->comps)
     t.add(cp.out, cp.in.data(), cp.in.size(), cp.count, p->osz, cp.unscaled ? kDescUnscaled : 0u);
-  const std::vector<char> host = t.image();
+  // a weighted plan: one weight pointer per compute behind the table
+  std::vector<char> host = t.image(p->weighted ? p->comps.size() * sizeof(const float *) : 0);
+  if (p->weighted) {
+    const float **w = (const float **)(host.data() + t.bytes());
+    for (size_t i = 0; i < p->comps.size(); i++) w[i] = p->comps[i].weights;
+  }
   if (int e = check_hip(hipMalloc((void **)&p->d_block, host.size()), "plan: hipMalloc")) return e;
   if (int e = check_hip(hipMemcpy(p->d_block, host.data(), host.size(), hipMemcpyHostToDevice), "plan: upload"))
     return e;
@@ -138,6 +146,7 @@ int plan_upload(hiccl_reduce_plan *p, hipStream_t s) {
   t.bind(p->args, p->d_block);
   p->args.t_begin = 0;
   p->args.t_end = t.units;
+  p->d_weights = p->weighted ? (const float *const *)(p->d_block + t.bytes()) : nullptr;
   p->dirty = false;
   return 0;
 }
@@ -149,9 +158,10 @@ int plan_kernel(hiccl_reduce_plan *p, hipStream_t s) {
   c.unroll = p->unroll;
   c.block = p->engine == HICCL_ENGINE_PHASE ? kPhBlock : kDefBlock;
   c.bpc = p->bpc;
-  PlanArgsScaled a;  // the plan itself is only read (hiccl_reduce_plan_enqueue from several threads)
+  PlanArgsWeighted a;  // the plan itself is only read (hiccl_reduce_plan_enqueue from several threads)
   (PlanArgs &)a = p->args;
   a.scale = p->kernel_scale();
+  a.weights = p->d_weights;
   return launch_plan(a, p->dtype, c, p->mean_n, p->device, s, plan_pol(p->eff_peer));
 }
 
@@ -299,14 +309,14 @@ int hiccl_reduce_plan_set_accumulate(hiccl_reduce_plan_t *p, int on) {
       return fail(hipErrorInvalidValue, "plan_set_accumulate: an accumulating plan takes no HICCL_PEER_STORES (the old output "
                                         "is read where it is written: keep it in local memory)");
     // the accumulating kernels are untuned, as the widened ones: the same shapes
-    const std::string why = plan_config_error(p, p->req, kOpWidenAccum);
+    const std::string why = plan_config_error(p, p->req, p->weighted ? kOpWeightedAccum : kOpWidenAccum);
     if (!why.empty())
       return fail(hipErrorInvalidValue,
                   "plan_set_accumulate: the plan's config names a shape the accumulating kernels lack: " + why);
   } else if (p->accumulate) {
     // back to the widened kernels, whose PHASE shape is not the accumulating
     // ones': a config that names the latter is refused here, not replaced
-    const std::string why = plan_config_error(p, p->req, kOpWidenSum);
+    const std::string why = plan_config_error(p, p->req, p->weighted ? kOpWeightedSum : kOpWidenSum);
     if (!why.empty())
       return fail(hipErrorInvalidValue,
                   "plan_set_accumulate: the plan's config names a shape the widened kernels lack: " + why);
@@ -318,6 +328,31 @@ int hiccl_reduce_plan_set_accumulate(hiccl_reduce_plan_t *p, int on) {
 }
 
 int hiccl_reduce_plan_accumulate(const hiccl_reduce_plan_t *p) { return !p ? -1 : p->accumulate ? 1 : 0; }
+
+int hiccl_reduce_plan_set_weighted(hiccl_reduce_plan_t *p, int on) {
+  if (!p) return fail(hipErrorInvalidValue, "plan_set_weighted: plan is NULL");
+  if (!p->comps.empty())
+    return fail(hipErrorInvalidValue, "plan_set_weighted: a plan is made weighted before the first add (the plan holds " +
+                                          std::to_string(p->comps.size()) + " computes)");
+  if (on && !p->widened)
+    return fail(hipErrorInvalidValue, "plan_set_weighted: only a widened plan is weighted (hiccl_reduce_plan_set_out_dtype "
+                                      "first): same-type weighted sums are not implemented");
+  // the weighted kernels come in the widened and accumulating ones' shapes, but
+  // their PHASE chunk is their own: a config that names another is refused
+  // here, never replaced
+  const int op = on ? (p->accumulate ? kOpWeightedAccum : kOpWeightedSum) : (p->accumulate ? kOpWidenAccum : kOpWidenSum);
+  if (p->widened) {
+    const std::string why = plan_config_error(p, p->req, op);
+    if (!why.empty())
+      return fail(hipErrorInvalidValue, std::string("plan_set_weighted: the plan's config names a shape the ") +
+                                            (on ? "weighted" : "unweighted") + " kernels lack: " + why);
+  }
+  if (p->weighted != (on != 0)) p->dirty = true;
+  p->weighted = on != 0;
+  return 0;
+}
+
+int hiccl_reduce_plan_weighted(const hiccl_reduce_plan_t *p) { return !p ? -1 : p->weighted ? 1 : 0; }
 
 int hiccl_reduce_plan_out_dtype(const hiccl_reduce_plan_t *p) {
   return !p ? -1 : p->widened ? (int)HICCL_FLOAT32 : p->dtype;
@@ -367,8 +402,13 @@ int hiccl_reduce_plan_set_config(hiccl_reduce_plan_t *p, const hiccl_reduce_conf
 int hiccl_reduce_plan_engine(const hiccl_reduce_plan_t *p) { return p ? p->engine : -1; }
 
 static int plan_add_impl(hiccl_reduce_plan_t *p, void *out, const void *const *in, int n, size_t count, bool unscaled,
-                         const std::string &who) {
+                         const std::string &who, const float *weights = nullptr, bool weighted = false) {
   if (!p) return fail(hipErrorInvalidValue, who + ": plan is NULL");
+  if (p->weighted && !weighted)
+    return fail(hipErrorInvalidValue, who + ": a weighted plan takes weighted computes only (hiccl_reduce_plan_add_weighted: "
+                                            "its kernels read n weights per compute)");
+  if (!p->weighted && weighted)
+    return fail(hipErrorInvalidValue, who + ": the plan is not weighted (hiccl_reduce_plan_set_weighted before the first add)");
   if (unscaled && p->widened)
     return fail(hipErrorInvalidValue, who + ": a widened or accumulating plan takes no unscaled compute (its kernels "
                                             "always multiply: one scale per plan)");
@@ -378,8 +418,11 @@ static int plan_add_impl(hiccl_reduce_plan_t *p, void *out, const void *const *i
   } else if (int e = check_buffers(out, in, n, count, p->esz)) {
     return e;
   }
+  if (weighted)
+    if (int e = check_weights(out, weights, n, count, who)) return e;
   if (count == 0) return 0;
   hiccl_reduce_plan::Comp c;
+  c.weights = weights;
   c.out = out;
   c.in.assign(in, in + n);
   c.count = count;
@@ -396,6 +439,11 @@ int hiccl_reduce_plan_add(hiccl_reduce_plan_t *p, void *out, const void *const *
 
 int hiccl_reduce_plan_add_unscaled(hiccl_reduce_plan_t *p, void *out, const void *const *in, int n, size_t count) {
   return plan_add_impl(p, out, in, n, count, true, "plan_add_unscaled");
+}
+
+int hiccl_reduce_plan_add_weighted(hiccl_reduce_plan_t *p, void *out, const void *const *in, const float *weights, int n,
+                                   size_t count) {
+  return plan_add_impl(p, out, in, n, count, false, "plan_add_weighted", weights, true);
 }
 
 int hiccl_reduce_plan_num_unscaled(const hiccl_reduce_plan_t *p) { return p ? (int)p->num_unscaled : 0; }
@@ -436,7 +484,7 @@ int hiccl_reduce_plan_launch_each(hiccl_reduce_plan_t *p, void *stream) {
     // an unscaled compute of a scaled plan is a plain sum (a widened plan has none)
     const bool plain = !p->widened && (!p->scaled || c.unscaled);
     if (int e = reduce_call(p->dtype, plain ? p->op : p->widened ? p->kernel_op() : kOpScaledSum, plain ? nullptr : &sc,
-                            c.out, c.in.data(), (int)c.in.size(), c.count, stream, &p->req))
+                            c.out, c.in.data(), (int)c.in.size(), c.count, stream, &p->req, c.weights))
       return e;
   }
   p->launched = true;

@@ -17,10 +17,12 @@ struct hiccl_reduce_plan {
   bool widened = false;           // hiccl_reduce_plan_set_out_dtype: dtype inputs, f32 outputs (op stays SUM)
   // the operator the policy and the kernel tables see
   bool accumulate = false;        // hiccl_reduce_plan_set_accumulate: out += (alpha *) sum, on a widened plan only
+  bool weighted = false;          // hiccl_reduce_plan_set_weighted: every compute brings n f32 weights in device memory
   // A scaled plan's family follows its computes: all scaled -- the scaled
   // kernels; all unscaled (hiccl_reduce_plan_add_unscaled) -- the plain SUM
   // kernels, tuned table included; both kinds -- the mixed kernels.
   int kernel_op() const {
+    if (weighted) return accumulate ? hiccl_impl::kOpWeightedAccum : hiccl_impl::kOpWeightedSum;
     if (widened) return accumulate ? hiccl_impl::kOpWidenAccum : hiccl_impl::kOpWidenSum;
     if (!scaled || num_unscaled == comps.size()) return op;
     return num_unscaled ? hiccl_impl::kOpMixedSum : hiccl_impl::kOpScaledSum;
@@ -45,12 +47,14 @@ struct hiccl_reduce_plan {
     std::vector<const void *> in;
     size_t count;
     bool unscaled = false;  // hiccl_reduce_plan_add_unscaled: the plain sum, whatever the plan's scale
+    const float *weights = nullptr;  // hiccl_reduce_plan_add_weighted: the caller's n floats, passed along
   };
   std::vector<Comp> comps;
   size_t num_unscaled = 0;  // computes with the flag
   bool dirty = true;
   char *d_block = nullptr;  // the uploaded DescTable
   hiccl_impl::PlanArgs args;  // pointers into d_block
+  const float *const *d_weights = nullptr;  // a weighted plan: one weight pointer per compute, behind the table in d_block
   hipStream_t own = nullptr;
   hipStream_t last = nullptr;  // stream of the last launch (plan_sync synchronises it)
   bool launched = false;
@@ -100,7 +104,8 @@ struct DescTable {
 // One plan-kernel launch of `a` (desc, ptrs, unit_comp, units, stride set),
 // shaped by `c` (engine and shape resolved), in cache policy `pol`.
 // (a.scale: the scale of a scaled sum, c.op == kOpScaledSum).
-int launch_plan(PlanArgsScaled a, int dtype, const Cfg &c, double mean_n, int dev, hipStream_t s, int pol);
+// (a.weights: the weight pointers of a weighted sum, which runs the kernels of pick_plan_weighted).
+int launch_plan(PlanArgsWeighted a, int dtype, const Cfg &c, double mean_n, int dev, hipStream_t s, int pol);
 
 // Before a device block is freed: no launch may still read it.  True if some
 // launch went out on a stream nobody remembered -- the device was synchronised.

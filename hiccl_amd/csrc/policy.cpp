@@ -96,7 +96,10 @@ constexpr uint64_t kPacedGridNum = 7, kPacedGridDen = 8;
 // operator: finish_cfg, unit_pkts, plan_shape_error).
 // A mixed plan (kOpMixedSum: scaled per compute) takes the scaled sum's: its
 // kernels are the scaled ones with a factor chosen per unit.
-inline int threshold_op(int op) { return op == kOpWidenAccum ? kOpWidenSum : op == kOpMixedSum ? kOpScaledSum : op; }
+// A weighted sum takes its unweighted family's, and so the widened sum's.
+inline int threshold_op(int op) {
+  return is_widen_op(op) ? kOpWidenSum : op == kOpMixedSum ? kOpScaledSum : op;
+}
 
 constexpr int kDefBpc = 1;
 constexpr int kSmallBpc = 4;
@@ -342,8 +345,8 @@ Cfg oneshot_cfg(int dtype, int op, const hiccl_reduce_config_t *cfg, uint64_t np
   if (!c.wt) return c;
   Cfg w = c;
   w.store = kPolStoreSys;
-  if (n > kMaxArgInputs ? pick_plan(dtype, w.acc, w.op, w.engine, w.unroll, plan_pol(HICCL_PEER_STORES)) != nullptr
-                        : single_for(dtype, w) != nullptr)
+  if (n > kMaxArgInputs ? has_plan(dtype, w.acc, w.op, w.engine, w.unroll, plan_pol(HICCL_PEER_STORES))
+                        : has_single(dtype, w))
     return w;
   c = raw;
   finish_cfg(c, npkt, n, dtype, dev);
@@ -376,7 +379,7 @@ std::string plan_shape_error(const Cfg &c, int dtype) {
   const bool wt = c.store == kPolStoreSys;
   if (wt && !wt_unroll(c.unroll))
     return "write-through plan kernels (store_policy 4) run the TILE engine at unroll 4 (f32 / bf16 / f16: 2 or 4) only";
-  if (!pick_plan(dtype, c.acc, c.op, HICCL_ENGINE_TILE, c.unroll, plan_pol(wt ? HICCL_PEER_STORES : 0)))
+  if (!has_plan(dtype, c.acc, c.op, HICCL_ENGINE_TILE, c.unroll, plan_pol(wt ? HICCL_PEER_STORES : 0)))
     return "plan kernels run the TILE engine at unroll 4 (f32 / bf16 / f16: 1, 2, 4, 8 or 16) only";
   return "";
 }

@@ -15,7 +15,7 @@ struct Cfg {
   bool wt;          // the launch stores write-through by size: decided BEFORE the engine
                     // (oneshot_cfg, plan_cfg), since AUTO's engine rules differ under it
   int order;        // tile-order segments (hiccl_reduce_config_t.order; 0/1 linear)
-  int op;           // hiccl_op_t, kOpWidenSum / kOpWidenAccum, or kOpScaledSum (a scaled sum: untuned, like every operator but
+  int op;           // hiccl_op_t, kOpWidenSum / kOpWidenAccum, kOpWeightedSum / kOpWeightedAccum, or kOpScaledSum (a scaled sum: untuned, like every operator but
                     // SUM, and honours acc): not a config entry -- the call or the plan names it
                     // (resolve: SUM)
   int pol() const { return store * 10 + nt; }
@@ -50,9 +50,15 @@ inline size_t out_esize(int dtype, int op) { return is_widen_op(op) ? 4 : esize(
 // The one-shot call behind hiccl_reduce_op (scale NULL, `op` checked by the
 // caller), hiccl_reduce_scaled (op kOpScaledSum) and hiccl_reduce_widened (op
 // kOpWidenSum, dtype the inputs', scale never NULL) and hiccl_reduce_accumulate
-// (op kOpWidenAccum, likewise): oneshot.cpp.
+// (op kOpWidenAccum, likewise) and hiccl_reduce_weighted (kOpWeightedSum /
+// kOpWeightedAccum, likewise, with `weights` -- n floats in device memory, which
+// every other op leaves NULL): oneshot.cpp.
 int reduce_call(int dtype, int op, const Scale *scale, void *out, const void *const *in, int n, size_t count,
-                void *stream, const hiccl_reduce_config_t *cfg);
+                void *stream, const hiccl_reduce_config_t *cfg, const float *weights = nullptr);
+// The weights of a weighted sum (n > 0: not NULL, 4-byte aligned, not
+// overlapping the count f32 outputs), refused as `who: ...` with
+// hipErrorInvalidValue before any device work.
+int check_weights(const void *out, const float *weights, int n, size_t count, const std::string &who);
 
 // Does a launch that writes `out_bytes` from `n` inputs per output (a plan's
 // packet-weighted mean) store write-through BY SIZE under the raw config?
@@ -70,6 +76,16 @@ Cfg oneshot_cfg(int dtype, int op, const hiccl_reduce_config_t *cfg, uint64_t np
 // Its kernel (n <= kMaxArgInputs), or NULL.
 inline single_fn single_for(int dtype, const Cfg &c) {
   return pick_single(dtype, c.acc, c.op, c.engine, c.block, c.unroll, c.pol());
+}
+// Is there one?  (A weighted op's kernels have a launcher type of their own.)
+inline bool has_single(int dtype, const Cfg &c) {
+  if (is_weighted_op(c.op)) return pick_single_weighted(dtype, c.acc, c.op, c.engine, c.block, c.unroll, c.pol()) != nullptr;
+  return single_for(dtype, c) != nullptr;
+}
+// Likewise of the plan kernels.
+inline bool has_plan(int dtype, int acc, int op, int engine, int unroll, int pol) {
+  if (is_weighted_op(op)) return pick_plan_weighted(dtype, acc, op, engine, unroll, pol) != nullptr;
+  return pick_plan(dtype, acc, op, engine, unroll, pol) != nullptr;
 }
 
 // The plan kernels' cache policy: nt loads and stores, or a plan's peer

@@ -169,6 +169,7 @@ bool tuned_type(int dtype, int acc, int op) {
 }
 
 int phase_p(int dtype, int acc, int op) {
+  if (is_weighted_op(op)) return phase_p_weighted(dtype, op);  // (reduce_weighted.hip)
   if (op == kOpWidenAccum) return phase_p_of<OpBF16AccF32>();  // the four accumulating ops alike
   if (is_f8(dtype)) return acc == HICCL_ACC_WIDE ? phase_p_of<OpF8Wide<kE4M3>>() : phase_p_of<OpF8<kE4M3>>();
   return with_elem_sum(dtype, acc, 16, [](auto e) { return phase_p_of<typename decltype(e)::Op>(); });
@@ -180,6 +181,7 @@ int phase_p(int dtype, int acc, int op) {
 // reduce_f8.hip; the widened sums (whose dtype is the inputs') from
 // reduce_widen.hip, the accumulating ones from reduce_accum.hip.
 single_fn pick_single(int dtype, int acc, int op, int engine, int block, int unroll, int pol) {
+  if (is_weighted_op(op)) return nullptr;  // pick_single_weighted: launchers of another type
   if (op == kOpWidenAccum) return pick_single_accum(dtype, acc, op, engine, block, unroll, pol);
   if (op == kOpWidenSum) return pick_single_widen(dtype, acc, op, engine, block, unroll, pol);
   if (is_f8(dtype)) return pick_single_f8(dtype, acc, op, engine, block, unroll, pol);
@@ -190,6 +192,7 @@ single_fn pick_single(int dtype, int acc, int op, int engine, int block, int unr
 }
 
 plan_fn pick_plan(int dtype, int acc, int op, int engine, int unroll, int pol) {
+  if (is_weighted_op(op)) return nullptr;  // pick_plan_weighted
   if (op == kOpMixedSum) return pick_plan_mixed(dtype, acc, op, engine, unroll, pol);  // (reduce_mixed.hip)
   if (op == kOpWidenAccum) return pick_plan_accum(dtype, acc, op, engine, unroll, pol);
   if (op == kOpWidenSum) return pick_plan_widen(dtype, acc, op, engine, unroll, pol);

@@ -10,7 +10,8 @@
 // with this one last, which the ISA tier of the scaled sums relies on.  The
 // widened sums' kernels (reduce_widen.hip) follow them, for the same reason,
 // and the accumulating widened sums' (reduce_accum.hip) follow those, and the
-// mixed plan kernels (reduce_mixed.hip) come last.
+// mixed plan kernels (reduce_mixed.hip) follow those, and the weighted widened
+// sums' (reduce_weighted.hip) come last.
 #include "engine.h"
 
 namespace hiccl_impl {
@@ -29,3 +30,4 @@ plan_fn pick_plan_scale(int dtype, int acc, int op, int engine, int unroll, int 
 #include "reduce_widen.hip"
 #include "reduce_accum.hip"
 #include "reduce_mixed.hip"
+#include "reduce_weighted.hip"

@@ -2,10 +2,11 @@
 // facts, synthetic inputs, stream copies, bucket allocations.
 #include "runtime.h"
 
-// 0.9.0 (0.2: HICCL_FLOAT16; 0.3: hiccl_op_t, MAX and MIN; 0.4: PROD, BAND, BOR, BXOR; 0.5: scaled sums;
+// 0.10.0 (0.2: HICCL_FLOAT16; 0.3: hiccl_op_t, MAX and MIN; 0.4: PROD, BAND, BOR, BXOR; 0.5: scaled sums;
 // 0.6: HICCL_FLOAT8_E4M3, HICCL_FLOAT8_E5M2; 0.7: widened sums;
-// 0.8: accumulating widened sums; 0.9: unscaled computes in a scaled plan, the mixed plan kernels)
-#define HICCL_VERSION_INT 900
+// 0.8: accumulating widened sums; 0.9: unscaled computes in a scaled plan, the mixed plan kernels;
+// 0.10: weighted widened sums)
+#define HICCL_VERSION_INT 1000
 
 using namespace hiccl_impl;
 

@@ -313,6 +313,12 @@ class Compute {
 // set_accumulate makes every start() ADD to the outputs instead of overwriting
 // them (hiccl_reduce_plan_set_accumulate): out = fl32(out + r), r the finished
 // (and scaled) sum -- an f32 master gradient accumulated over micro-batches.
+// add(in, out, n, compid, weights) makes the object WEIGHTED
+// (hiccl_reduce_plan_set_weighted): input k of the compute counts as
+// fl32(weights[k] * widen(x)), the product and the add rounded separately.  The
+// weights are in.size() floats in DEVICE memory that every start() reads anew
+// (on the host port: host memory, read by start() likewise).  The first add
+// decides: an object takes weighted adds only, or none.
 // A Comm<T> schedule has no use for it (a schedule moves T between ranks, and
 // a widened sum changes type inside the tree: INTEGRATION.md).
 template <typename T>
@@ -336,7 +342,24 @@ class WidenCompute {
 
   // As Compute<T>::add, with a float output.
   void add(std::vector<T *> &in, float *out, size_t n, int compid, bool peer_inputs = false) {
+    add_impl(in, out, n, compid, nullptr, false, peer_inputs);
+  }
+
+  // The weighted form: `weights` are in.size() floats (device memory; host
+  // memory on the host port), kept by pointer and read by every start().
+  void add(std::vector<T *> &in, float *out, size_t n, int compid, const float *weights, bool peer_inputs = false) {
+    add_impl(in, out, n, compid, weights, true, peer_inputs);
+  }
+
+ private:
+  void add_impl(std::vector<T *> &in, float *out, size_t n, int compid, const float *weights, bool with_weights,
+                bool peer_inputs) {
     if (CommBench::myid != compid) return;
+    if (numcomp && with_weights != weighted)
+      CommBench::die("WidenCompute::add", weighted ? "a weighted object takes weighted adds only (the first add decided)"
+                                                   : "the object is not weighted (the first add decided)");
+    weighted = with_weights;
+    weightbuf.push_back(weights);
     inputbuf.push_back(in);
     outputbuf.push_back(out);
     count.push_back(n);
@@ -350,16 +373,23 @@ class WidenCompute {
         check(hiccl_reduce_plan_set_engine(plan, eng), "plan_set_engine");
       }
       check(hiccl_reduce_plan_set_out_dtype(plan, HICCL_FLOAT32), "plan_set_out_dtype");  // before the first add
+      if (weighted) check(hiccl_reduce_plan_set_weighted(plan, 1), "plan_set_weighted");  // likewise
       if (scaled) check(hiccl_reduce_plan_set_scale(plan, &scale), "plan_set_scale");
       if (accumulating) check(hiccl_reduce_plan_set_accumulate(plan, 1), "plan_set_accumulate");
     }
     if (peer_inputs && !(hiccl_reduce_plan_peer(plan) & HICCL_PEER_LOADS))
       check(hiccl_reduce_plan_set_peer(plan, hiccl_reduce_plan_peer(plan) | HICCL_PEER_LOADS), "plan_set_peer");
-    check(hiccl_reduce_plan_add(plan, out, (const void *const *)in.data(), (int)in.size(), n), "plan_add");
+    if (weighted)
+      check(hiccl_reduce_plan_add_weighted(plan, out, (const void *const *)in.data(), weights, (int)in.size(), n),
+            "plan_add_weighted");
+    else
+      check(hiccl_reduce_plan_add(plan, out, (const void *const *)in.data(), (int)in.size(), n), "plan_add");
 #else
     (void)peer_inputs;
 #endif
   }
+
+ public:
 
   // out = fl32(sum * (float)alpha) from the next start() on; alpha finite, as a float too.
   void set_scale(double alpha) {
@@ -396,17 +426,19 @@ class WidenCompute {
       T *const *in = inputbuf[c].data();
       const int k = (int)inputbuf[c].size();
       const size_t n = count[c];
+      const float *w = weightbuf[c];
       if (accumulating) {
 #pragma omp parallel for schedule(static)
         for (size_t i = 0; i < n; i++) {
           // r in a statement of its own (and volatile, as widen_sum's partial
           // sums): a contracting compiler cannot fuse the multiply with the add
-          volatile float r = widen_sum<T>(in, k, i, scaled, scale);
+          volatile float r = weighted ? weighted_widen_sum<T>(in, w, k, i, scaled, scale) : widen_sum<T>(in, k, i, scaled, scale);
           out[i] = out[i] + r;
         }
       } else {
 #pragma omp parallel for schedule(static)
-        for (size_t i = 0; i < n; i++) out[i] = widen_sum<T>(in, k, i, scaled, scale);
+        for (size_t i = 0; i < n; i++)
+          out[i] = weighted ? weighted_widen_sum<T>(in, w, k, i, scaled, scale) : widen_sum<T>(in, k, i, scaled, scale);
       }
     }
 #endif
@@ -478,6 +510,8 @@ class WidenCompute {
   bool scaled = false;
   double scale = 1.0;
   bool accumulating = false;  // set_accumulate
+  bool weighted = false;      // the first add decides
+  std::vector<const float *> weightbuf;  // per compute: its weights, or NULL
 #ifndef HICCL_PORT_HOST
   hiccl_reduce_plan_t *plan = nullptr;
   static void check(int e, const char *what) {

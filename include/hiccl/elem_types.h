@@ -223,6 +223,21 @@ inline float widen_sum(T *const *in, int k, size_t i, bool scaled, double alpha)
   return scaled ? scale_finish<float>(acc, alpha) : (float)acc;
 }
 
+// One element of a WEIGHTED widened sum: input j counts as fl32(w[j] *
+// widen(in[j][i])), a product rounded to f32 -- it goes into a volatile float
+// in a statement of its own, so a contracting compiler cannot fuse it with the
+// add that follows (a fused multiply-add rounds once: another word).
+template <typename T>
+inline float weighted_widen_sum(T *const *in, const float *w, int k, size_t i, bool scaled, double alpha) {
+  static_assert(widenable<T>(), "HiCCL::weighted_widen_sum: bf16, f16 (_Float16), f8e4m3 or f8e5m2 inputs only");
+  volatile float acc = 0.0f;
+  for (int j = 0; j < k; j++) {
+    volatile float t = w[j] * (float)in[j][i];
+    acc = acc + t;
+  }
+  return scaled ? scale_finish<float>(acc, alpha) : (float)acc;
+}
+
 }  // namespace HiCCL
 
 #endif  // HICCL_ELEM_TYPES_H

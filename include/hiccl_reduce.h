@@ -390,6 +390,54 @@ int hiccl_reduce_auto_choice_accumulate(int in_dtype, const hiccl_reduce_config_
                                         int *store_policy);
 
 /* ----------------------------------------------------------------------
+ * Weighted widened sums: out = sum of w[k] * x[k], one f32 weight PER INPUT
+ * (NCCL's PreMulSum) -- FP8 or loss-scaled fp16 buckets that were quantised
+ * with a scale of their own each, dequantised and summed in one pass, with no
+ * f32 copy of any input.  Everything hiccl_reduce_widened says holds (dtypes,
+ * alpha, buffer rules, the layout, the store-form rule, n > 64 on the plan
+ * kernel with the caller's weight pointer passed along, n <= 64 capturable),
+ * and with `accumulate` non-zero everything hiccl_reduce_accumulate says.
+ * With w[k] the weights and widen() the exact f32 value of an element:
+ *
+ *   t[k][i]  fl32(w[k] * widen(x[k][i]))       one IEEE f32 multiply
+ *   s32[i]   (((+0.0f + t[0][i]) + t[1][i]) + ...) + t[n-1][i]
+ *   r[i]     s32[i] (alpha == NULL), or fl32(s32[i] * a32)
+ *   out[i]   r[i], or accumulating fl32(p[i] + r[i])
+ *
+ * The multiply and the add are TWO separately rounded operations, never a fused
+ * multiply-add: the words are the ones the caller's own two-pass path gives
+ * (f32 copies x[k].float() * w[k], then the f32 SUM of the copies).  Subnormals
+ * are kept in the product and in the sum, Inf + -Inf is NaN, NaNs compare by
+ * NaN-ness, nothing is clamped.  A weight of exactly 1.0f gives t = widen(x)
+ * bit for bit: all-ones weights give hiccl_reduce_widened's words.
+ * THE WEIGHTS are n consecutive floats in LOCAL DEVICE memory, 4-byte aligned,
+ * READ WHEN THE KERNEL RUNS (scalar loads): values written by an earlier kernel
+ * or copy on the same stream are seen, no host synchronisation is needed, and
+ * a captured graph replays with the values the memory then holds.  They are
+ * NOT VALIDATED: a zero weight gives +-0 (a NaN against an infinite element),
+ * an infinite or NaN weight follows IEEE.  They must not be written while a
+ * launch that reads them is in flight.  Refused with hipErrorInvalidValue,
+ * before any device work: weights NULL with n > 0, misaligned, or overlapping
+ * the output.  n == 0 behaves as the unweighted call (weights may be NULL);
+ * count == 0 is a no-op.
+ * The kernels' shapes are the widened sums' (overwriting: PHASE 512 x 16) and
+ * the accumulating sums' (PHASE 512 x 8).
+ * hiccl_reduce_auto_choice_weighted answers what hiccl_reduce_auto_choice_widened
+ * / _accumulate answer, by the same rules and thresholds (none of its own).
+ * Not covered: same-type weighted sums (f32 / f64 inputs, narrow outputs),
+ * weights in host memory, per-element or per-block scales (MX formats), the
+ * host pipe, programs, Comm<T>.
+ * Stands in for: no reference entry.  The arithmetic is the reference's
+ * reduce_kernel<float> (compute.h:14-23) applied to the pre-multiplied rows
+ * t[k]. */
+int hiccl_reduce_weighted(int in_dtype, int out_dtype, const double *alpha, int accumulate, void *out,
+                          const void *const *in, const float *weights, int n, size_t count, void *stream,
+                          const hiccl_reduce_config_t *cfg);
+int hiccl_reduce_auto_choice_weighted(int in_dtype, int accumulate, const hiccl_reduce_config_t *cfg, size_t count,
+                                      double n, int cus, int *engine, int *unroll, int *blocks_per_cu, int *dynamic,
+                                      int *store_policy);
+
+/* ----------------------------------------------------------------------
  * Persistent plan: the C-ABI counterpart of the reference's Compute<T>
  * (compute.h:26-204).  A plan holds any number of registered computes and
  * launches ALL of them in ONE kernel (one launch per pipeline step instead
@@ -486,6 +534,24 @@ int hiccl_reduce_plan_out_dtype(const hiccl_reduce_plan_t *plan);
  * plan.  hiccl_reduce_plan_accumulate: 1 / 0, -1 for NULL. */
 int hiccl_reduce_plan_set_accumulate(hiccl_reduce_plan_t *plan, int on);
 int hiccl_reduce_plan_accumulate(const hiccl_reduce_plan_t *plan);
+/* Weights (hiccl_reduce_weighted): with `on` non-zero every compute of a WIDENED
+ * plan brings n f32 weights in device memory (hiccl_reduce_plan_add_weighted)
+ * and writes the weighted sum; the plan's device block gains one weight pointer
+ * per compute, and the weights are read at every launch, enqueue, launch_each
+ * and graph replay: overwrite them in place between launches and the next
+ * launch follows.  Set BEFORE THE FIRST ADD, as set_out_dtype.  set_scale and
+ * set_accumulate work as on a widened plan (an accumulating weighted plan
+ * refuses HICCL_PEER_STORES likewise); a config that names the other family's
+ * PHASE shape is refused, never replaced.  Refused, before any device work: a
+ * plan that is not widened, a plan that holds computes.  A weighted plan
+ * refuses hiccl_reduce_plan_add and _add_unscaled, an unweighted plan
+ * hiccl_reduce_plan_add_weighted.  hiccl_reduce_plan_bytes prices a weighted
+ * compute as its widened or accumulating form: the 4 * n bytes of weights are
+ * NOT counted.  hiccl_program_add_plan keeps refusing the plan.
+ * hiccl_reduce_plan_weighted: 1 / 0, -1 for NULL.
+ * Stands in for: no reference entry (compute.h:14-23 on pre-multiplied rows). */
+int hiccl_reduce_plan_set_weighted(hiccl_reduce_plan_t *plan, int on);
+int hiccl_reduce_plan_weighted(const hiccl_reduce_plan_t *plan);
 /* Engine for the plan's launches (hiccl_engine_t; default AUTO, decided from
  * the total packets of all computes at the first launch after an add). */
 int hiccl_reduce_plan_set_engine(hiccl_reduce_plan_t *plan, int engine);
@@ -554,6 +620,13 @@ int hiccl_reduce_plan_add(hiccl_reduce_plan_t *plan, void *out, const void *cons
 int hiccl_reduce_plan_add_unscaled(hiccl_reduce_plan_t *plan, void *out, const void *const *in, int n,
                                    size_t count);
 int hiccl_reduce_plan_num_unscaled(const hiccl_reduce_plan_t *plan);
+/* hiccl_reduce_plan_add on a weighted plan (hiccl_reduce_plan_set_weighted):
+ * `weights` are the compute's n floats in device memory, under
+ * hiccl_reduce_weighted's rules and refusals (NULL with n > 0, misaligned,
+ * overlapping `out`).  The pointer is kept, not the values.
+ * Stands in for: no reference entry (compute.h:14-23 on pre-multiplied rows). */
+int hiccl_reduce_plan_add_weighted(hiccl_reduce_plan_t *plan, void *out, const void *const *in, const float *weights,
+                                   int n, size_t count);
 int hiccl_reduce_plan_launch(hiccl_reduce_plan_t *plan, void *stream);
 /* launch without remembering the stream for hiccl_reduce_plan_sync: for
  * stream-ordered callers that synchronise the stream themselves, and for
